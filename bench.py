@@ -13,12 +13,19 @@ Multi-GPU (torchrun, one rank per GPU): the film is cut into square tiles
 dealt round-robin to the ranks (tile t -> rank t % N); every rank renders all 32
 iterations of its tiles, packs them, and an RCCL gather over xGMI brings the
 packed tiles to rank 0, which assembles the frame.  Total work is fixed, so
-scaling is "strong".  At every N the line also carries `config5`: BASELINE
+scaling is "strong".  With --full the line also carries, at every N, `config5`: BASELINE
 config 5's stand-in (S-deep at 4096x4096, 64 spp) rendered the
 same way, tile-sharded over the N ranks and gathered; at N > 1 both carry a
 per-rank breakdown (`ranks`: frame / pack / gather ms and rays per rank) and
 `frame_equals_single_gpu` (the gathered frame against rank 0's whole-frame
 render, bit for bit).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times
+the N steps and prints the headline line; `--dump-outputs DIR` also writes the
+last timed frame.  Everything else -- the rooflines and their instrumented and
+isolated passes, the CPU baseline and parity, the suite scenes, the config-5
+line, and at N > 1 the per-rank breakdown and the bit-exact frame check -- runs
+only with `--full`.
 
 Output: ONE JSON line on rank 0.
 """
@@ -48,6 +55,13 @@ def parse():
     ap.add_argument("--spp", type=int, default=256)
     ap.add_argument("--spi", type=int, default=8)
     ap.add_argument("--size", type=int, default=0, help="square film size overriding the scene's (config 5: 4096)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: rooflines (instrumented and isolated passes), "
+                         "CPU baseline and parity, the suite scenes, the config-5 line, and at N > 1 the per-rank "
+                         "breakdown and the frame check; the options below select among these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed frame as DIR/framebuffer.npy (H x W x 3 float32) "
+                         "and its iteration count as DIR/iterations.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU baseline sample length")
     ap.add_argument("--suite", type=int, default=1, help="also measure the other §8d scenes (N=1 only)")
@@ -570,6 +584,18 @@ class RankFrames:
         return {"elapsed": elapsed, "stats": st, "totals": totals,
                 "slot_bytes": [int(d.stats()["slot_bytes"]) for d in self.devs]}
 
+    def last_frame(self):
+        """What a caller of the timed path holds after its last frame: the
+        film (H x W x 3 float32) and the iterations accumulated in it.  N = 1:
+        the handle's framebuffer; N > 1: the frame rank 0 assembled from the
+        gathered tiles (None on the other ranks)."""
+        if self.n == 1:
+            fb, it = self.devs[0].framebuffer(self.W * self.H * 3)
+            return fb.reshape(self.H, self.W, 3), it
+        if self.rank != 0:
+            return None, self.iters
+        return self.frame.cpu().numpy().reshape(self.H, self.W, 3), self.iters
+
     def breakdown(self):
         """One more frame, untimed for `value`, by phase on every rank: render
         (all iterations of the rank's tiles, to completion), pack, then -- after
@@ -732,26 +758,35 @@ def main():
     params = rf.params
     m = rf.measure(args.steps, args.warmup)
     elapsed, st, totals = m["elapsed"], m["stats"], m["totals"]
-    ranks = rf.breakdown() if n_gpus > 1 else None
-    frame_check = rf.check() if n_gpus > 1 and not args.no_check_frame else None
+    if args.dump_outputs:
+        # before any further pass renders into the handle: the last timed frame
+        fb, fb_iters = rf.last_frame()
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "framebuffer.npy"), np.ascontiguousarray(fb, dtype=np.float32))
+            np.save(os.path.join(args.dump_outputs, "iterations.npy"), np.array([fb_iters], dtype=np.float64))
+    full = args.full
+    ranks = rf.breakdown() if full and n_gpus > 1 else None
+    frame_check = rf.check() if n_gpus > 1 and (full or args.check_frame) and not args.no_check_frame else None
 
-    # ---- roofline of the dominant kernel, live HIP-event timing ----
-    scene_key = os.path.splitext(os.path.basename(args.scene))[0]
-    roof = roofline(dev, st, lambda: dev.render(params(0)), n_gpus, scene_key)
-    inst = roof.pop("_inst", None)
-    roof_shadow = None
-    if args.isolated and st["launches_trace"] == 0:
-        def frame():
-            dev.clear()
-            dev.render_iterations(params(0), iters)
-        isolated_extend(dev, frame, roof)
-        si = roof.pop("_si")
-        if n_gpus == 1 and si["launches_shadow"] > 0:
-            roof_shadow = fused_shadow_roofline(st, inst, si, scene_key)
-    roof["note"] = ("achieved counts the HBM bytes the kernel must move (path / radiance / shadow-ray streams; "
-                    "table reads too when the tables exceed the Infinity Cache); traffic is the rocprofv3 PMC "
-                    "measurement of the same kernel and workload; memory_system_gbs counts every table read "
-                    "including LDS / cache hits (a work rate)")
+    roof = roof_shadow = None
+    if full:
+        # ---- roofline of the dominant kernel, live HIP-event timing ----
+        scene_key = os.path.splitext(os.path.basename(args.scene))[0]
+        roof = roofline(dev, st, lambda: dev.render(params(0)), n_gpus, scene_key)
+        inst = roof.pop("_inst", None)
+        if args.isolated and st["launches_trace"] == 0:
+            def frame():
+                dev.clear()
+                dev.render_iterations(params(0), iters)
+            isolated_extend(dev, frame, roof)
+            si = roof.pop("_si")
+            if n_gpus == 1 and si["launches_shadow"] > 0:
+                roof_shadow = fused_shadow_roofline(st, inst, si, scene_key)
+        roof["note"] = ("achieved counts the HBM bytes the kernel must move (path / radiance / shadow-ray streams; "
+                        "table reads too when the tables exceed the Infinity Cache); traffic is the rocprofv3 PMC "
+                        "measurement of the same kernel and workload; memory_system_gbs counts every table read "
+                        "including LDS / cache hits (a work rate)")
 
     result = None
     if rank == 0:
@@ -760,10 +795,10 @@ def main():
         samples = float(W * H * iters * spi * args.steps)
         cpu = None
         parity = None
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if full and n_gpus == 1 and not args.no_cpu_baseline:
             cpu, parity = cpu_baseline(scene, dev, W, H, spi, args.cpu_seconds)
         suite = None
-        if n_gpus == 1 and args.suite:
+        if full and n_gpus == 1 and args.suite:
             # other scenes of SURVEY.md §8d, incl. the HBM roofline scene of record (S-soup-16M)
             suite = [suite_line(ignis_amd, 0, os.path.join(ROOT, "scenes", f), spi, n, size, bool(args.isolated))
                      for f, n, size in (("primitives.json", 8, None),
@@ -787,6 +822,7 @@ def main():
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "strong",
@@ -819,7 +855,7 @@ def main():
         result["slot_bytes_per_handle"] = m["slot_bytes"]
         result["backend"] = ("gloo (rehearsal)" if rehearsal else "nccl (RCCL)") if n_gpus > 1 else None
     rf.close()
-    if args.config5:
+    if full and args.config5:
         # BASELINE config 5 stand-in (S-deep at 4096x4096, 64 spp),
         # measured the same way at every N: tile-sharded over the ranks, gathered
         # to rank 0, per-rank breakdown (the headline frame above is config 2)

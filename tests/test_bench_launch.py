@@ -64,6 +64,18 @@ def _bench_module():
     return mod
 
 
+def test_full_and_dump_outputs_are_off_by_default(monkeypatch):
+    """A plain run measures the headline only: --full and --dump-outputs are
+    options, off unless given."""
+    b = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
 def test_limiters_come_from_committed_counter_profiles():
     """Every `limiter` string of the bench line is derived from a committed
     round-6 SQ/TCC summary of the same workload (bench.py sq_limiter), and the

@@ -1065,6 +1065,45 @@ def test_igcli_camera_orientation_matches_api(tmp_path, diamond_path, root):
     assert not np.array_equal(plain, ref)
 
 
+def test_bench_plain_run_dumps_last_frame(tmp_path, diamond_path, root):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times N steps and prints
+    the headline line without any of the --full measurements; --dump-outputs
+    writes the last timed frame, which equals the API render of the same frame
+    bit for bit (same arguments, same inputs, same outputs)."""
+    import subprocess
+    import sys
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--size", "96", "--spp", "8", "--spi", "4", "--dump-outputs", str(out)],
+                       check=True, timeout=120, capture_output=True, text=True)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["full"] is False
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    # N steps were timed: the rays of the line are two frames' worth of camera rays
+    assert line["rays"]["camera"] == 2 * 96 * 96 * 8
+    total = sum(line["rays"].values())
+    # ms_per_step is printed to 1e-3 ms and a step of this frame takes well over 0.1 ms
+    assert line["value"] == pytest.approx(total / (2 * line["ms_per_step"] * 1e-3) / 1e6, rel=1e-2)
+    for key in ("roofline", "roofline_shadow", "cpu_baseline", "parity", "suite"):
+        assert line[key] is None, key
+    assert "config5" not in line
+    fb = np.load(out / "framebuffer.npy")
+    assert fb.dtype == np.float32 and fb.shape == (96, 96, 3)
+    assert np.load(out / "iterations.npy").tolist() == [2.0]
+    dev = ignis_amd.Device(0)
+    dev.upload(ignis_amd.Scene.from_file(diamond_path))
+    p = ignis_amd.RenderParams()
+    p.width, p.height, p.spi = 96, 96, 4
+    dev.render_iterations(p, 2)
+    ref, it = dev.framebuffer(96 * 96 * 3)
+    dev.close()
+    assert it == 2
+    np.testing.assert_array_equal(fb.reshape(-1), ref)
+
+
 def test_image_parity_materials(device, root):
     """§8f wider materials: mirror, smooth / rough conductors (VNDF-GGX, GGX, Beckmann,
     anisotropic), smooth / rough plastic, Oren-Nayar, glass -- GPU vs oracle."""

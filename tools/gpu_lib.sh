@@ -17,8 +17,9 @@ gpu_tests() {
   return $rc
 }
 
-# the default bench (headline + suite + CPU baseline + config-5 line); extra args pass through
+# the full bench (bench.py --full: headline + rooflines + suite + CPU baseline + config-5 line); extra args pass through
 gpu_bench() {
+  set -- --full "$@"
   timeout -k 10 700 python3 bench.py "$@" > gpurun_out/bench.json 2> gpurun_out/bench.err
   local rc=$?; head -c 400 gpurun_out/bench.json; echo
   [ $rc -eq 0 ] || tail -5 gpurun_out/bench.err
@@ -69,7 +70,7 @@ gpu_stats() {
 # the launcher's N-rank rehearsal on one GPU (gloo, every rank on GPU 0)
 gpu_rehearse() {
   local n=${1:-2}
-  IGX_BENCH_REHEARSAL=1 timeout -k 10 600 python3 bench.py --gpus $n --steps 2 --warmup 1 --config5-steps 1 \
+  IGX_BENCH_REHEARSAL=1 timeout -k 10 600 python3 bench.py --gpus $n --full --steps 2 --warmup 1 --config5-steps 1 \
     > gpurun_out/rehearse$n.json 2> gpurun_out/rehearse$n.err
   local rc=$?; grep -o '"frame_equals_single_gpu": [a-z]*' gpurun_out/rehearse$n.json | tr '\n' ' '; echo
   [ $rc -eq 0 ] || tail -5 gpurun_out/rehearse$n.err
