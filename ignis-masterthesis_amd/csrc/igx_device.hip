@@ -29,6 +29,7 @@
 #include "igx_kernels.h"
 #include "../host/bvh_build.h"
 #include "../host/light_select.h"
+#include "../host/lds_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -53,7 +54,7 @@ using namespace igxd;
 // kernel instantiations build in parallel:
 //   0 = host driver, C-ABI and the small kernels; 1 = k_extend variants;
 //   2 = k_finish variants; 3 = k_trace / k_trace_refill / k_shade / k_shadow /
-//   k_shadow_refill variants.  Types and device functions are shared; each
+//   k_shadow_refill variants; 4 = the wide (BLOCK_WIDE-thread) k_extend variants.  Types and device functions are shared; each
 //   part instantiates only its own launch helpers (explicit instantiation),
 //   the others see them as extern templates.
 #ifndef IGX_PART
@@ -63,6 +64,12 @@ using namespace igxd;
 namespace igxh {
 
 constexpr int BLOCK = 256;
+// The LDS-staged k_extend also comes with one 1024-thread block per CU: one
+// copy of the traversal tables instead of four leaves LDS for the shading
+// tables (stage_scene_lds; layout chosen per scene, host/lds_plan.h).  Every
+// other kernel runs BLOCK threads.
+constexpr int BLOCK_WIDE = LDS_PLAN_BLOCK_WIDE;
+static_assert(BLOCK == LDS_PLAN_BLOCK, "host/lds_plan.h plans for BLOCK-thread blocks");
 [[maybe_unused]] constexpr int MAX_BLOCKS_PER_CU = 8;  // 2048 threads per CU; grids never exceed num_cus * this
 [[maybe_unused]] constexpr int MAX_STACK = 128;        // traversal stack entries (LDS + spill) per ray
 constexpr int MAX_BOUNCES = 256;          // path depth is stored in 8 bits (p1.w, above the 24-bit RNG counter)
@@ -254,9 +261,13 @@ __device__ __forceinline__ int row_total(const int* row) {
 struct WaveWork {
     int s, k, K;
 };
+// BT: threads per block of the launch (grids are multiples of NSH / (BT / 64) blocks)
+template <int BT = BLOCK>
 __device__ __forceinline__ WaveWork wave_work() {
-    const int g = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES_PER_BLOCK + (int)(threadIdx.x >> 6));
-    return WaveWork{g % NSH, g / NSH, (int)gridDim.x * WAVES_PER_BLOCK / NSH};
+    constexpr int WPB = BT / 64;
+    static_assert(BT % 64 == 0 && NSH % WPB == 0, "a block's waves divide the shards");
+    const int g = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WPB + (int)(threadIdx.x >> 6));
+    return WaveWork{g % NSH, g / NSH, (int)gridDim.x * WPB / NSH};
 }
 
 // Storage index of path i of a freshly generated chunk: consecutive groups of
@@ -902,26 +913,30 @@ __device__ __forceinline__ PathState camera_path(const FrameArgs& fa, const Scen
 // rays to the same shard of the output streams (wave_append_paths): no block
 // barrier, so a wave whose rays finish early moves on to its next 64 paths.
 // ---------------------------------------------------------------------------
-template <int V0, bool STATS, bool LDS>
-__global__ void __launch_bounds__(BLOCK, LDS ? EXTEND_WAVES_LDS : (variant_full(V0) ? EXTEND_WAVES_FULL : EXTEND_WAVES)) k_extend(FrameArgs fa, SceneView gsv, PathBuf in, PathBuf out, ShadowBuf sh,
+// BT threads per block: BLOCK, or BLOCK_WIDE for the LDS-staged kernel with
+// the shading tables staged too (16 waves, 4 per SIMD: the same 128-VGPR cap).
+template <int V0, bool STATS, bool LDS, int BT = BLOCK>
+__global__ void __launch_bounds__(BT, LDS ? EXTEND_WAVES_LDS : (variant_full(V0) ? EXTEND_WAVES_FULL : EXTEND_WAVES)) k_extend(FrameArgs fa, SceneView gsv, PathBuf in, PathBuf out, ShadowBuf sh,
                                                   float4* L, KernelCounters kc, int tail_threshold) {
-    constexpr int V = LDS ? kernel_variant(V0, true) : (EXTEND_TREELET ? kernel_variant(V0, false) : V0); // LDS-staged nodes: padded stride; global tables: treelet (device_scene.h) or global node loads
-    __shared__ int stack_mem[LDS_STACK * BLOCK];
+    static_assert(BT == BLOCK || (LDS && BT == BLOCK_WIDE), "the wide block is the LDS-staged kernel's");
+    constexpr bool SHADE_LDS = BT > BLOCK; // the wide block stages the shading tables too
+    constexpr int V = LDS ? kernel_variant(V0, true) : (EXTEND_TREELET ? kernel_variant(V0, false) : V0); // LDS-staged tables: bit 3 (node steps skip the stack-top peek); global tables: treelet (device_scene.h) or global node loads
+    __shared__ int stack_mem[LDS_STACK * BT];
     extern __shared__ float4 lds_scene[];
-    const TStack ts = make_tstack(stack_mem, LDS_STACK, gsv.spill);
+    const TStack ts = make_tstack<BT>(stack_mem, LDS_STACK, gsv.spill);
     // gen_n > 0 (bounce 0 with generation fused; the host launches it only
     // when n > tail): the paths are the chunk's camera paths in k_generate's
     // shard order, built here instead of being read from the input stream.
     const bool gen = fa.gen_n > 0;
     if (!gen && row_total(kc.cnt_in) <= tail_threshold) return; // k_finish takes the remaining paths (block-uniform)
-    const SceneView sv = LDS ? stage_scene_lds<BLOCK>(gsv, lds_scene) : stage_treelet<BLOCK>(gsv, lds_scene);
+    const SceneView sv = LDS ? stage_scene_lds<BT, SHADE_LDS>(gsv, lds_scene) : stage_treelet<BT>(gsv, lds_scene);
     TraceStats st{0, 0, 0, 0, 0, 0, 0};
-    __shared__ unsigned long long cls_mem[STATS ? WAVES_PER_BLOCK * 36 : 1]; // per-class counters (instrumented)
+    __shared__ unsigned long long cls_mem[STATS ? BT / 64 * 36 : 1]; // per-class counters (instrumented), 36 per wave
     if constexpr (STATS) {
         st.cls = cls_mem + 36 * (threadIdx.x >> 6);
         if (lane_id() < 36) st.cls[lane_id()] = 0;
     }
-    const WaveWork w = wave_work();
+    const WaveWork w = wave_work<BT>();
     // Groups of 64 positions of shard s: statically every K-th group from
     // the wave's own (grid-stride), or (fa.dynamic) the next group a shard
     // counter hands out, moving on to the following shards once the own is
@@ -1017,7 +1032,7 @@ __global__ void __launch_bounds__(BLOCK, LDS ? EXTEND_WAVES_LDS : (variant_full(
 template <int V0, bool STATS, int WAVES, bool LDS>
 __global__ void __launch_bounds__(BLOCK, WAVES) k_trace(FrameArgs fa, SceneView gsv, PathBuf in, HitBuf hits,
                                                       const int* cnt, int tail_threshold, unsigned long long* stats) {
-    constexpr int V = LDS ? kernel_variant(V0, true) : V0; // LDS-staged nodes: padded stride; global tables: global node loads (no treelet)
+    constexpr int V = LDS ? kernel_variant(V0, true) : V0; // LDS-staged tables: bit 3 (node steps skip the stack-top peek); global tables: global node loads (no treelet)
     __shared__ int stack_mem[LDS_STACK * BLOCK];
     extern __shared__ float4 lds_scene[];
     const TStack ts = make_tstack(stack_mem, LDS_STACK, gsv.spill);
@@ -1105,7 +1120,7 @@ template <int V0, bool STATS, bool LDS>
 __global__ void __launch_bounds__(BLOCK) k_finish(FrameArgs fa, SceneView gsv, PathBuf in, float4* L, const int* cnt,
                                                   int tail_threshold, unsigned long long* stats,
                                                   unsigned long long* tail_counts) {
-    constexpr int V = LDS ? kernel_variant(V0, true) : V0; // LDS-staged nodes: padded stride; global tables: global node loads (the tail kernel stages no treelet)
+    constexpr int V = LDS ? kernel_variant(V0, true) : V0; // LDS-staged tables: bit 3 (node steps skip the stack-top peek); global tables: global node loads (the tail kernel stages no treelet)
     __shared__ int stack_mem[LDS_STACK * BLOCK];
     extern __shared__ float4 lds_scene[];
     const TStack ts = make_tstack(stack_mem, LDS_STACK, gsv.spill);
@@ -1339,7 +1354,7 @@ __device__ __forceinline__ bool shadow_walk(const SceneView& sv, const TStack& t
 template <int V0, bool STATS, bool LDS>
 __global__ void __launch_bounds__(BLOCK) k_shadow(SceneView gsv, ShadowBuf sh, float4* L, const int* cnt,
                                                   unsigned long long* stats, int* work) {
-    constexpr int V = LDS ? kernel_variant(V0, true) : (SHADOW_TREELET ? kernel_variant(V0, false) : V0); // LDS-staged nodes: padded stride; global tables: treelet or global node loads
+    constexpr int V = LDS ? kernel_variant(V0, true) : (SHADOW_TREELET ? kernel_variant(V0, false) : V0); // LDS-staged tables: bit 3 (node steps skip the stack-top peek); global tables: treelet or global node loads
     __shared__ int stack_mem[LDS_STACK * BLOCK];
     extern __shared__ float4 lds_scene[];
     const TStack ts = make_tstack(stack_mem, LDS_STACK, gsv.spill);
@@ -1540,7 +1555,7 @@ template <int V0, bool STATS, bool LDS>
 __global__ void __launch_bounds__(BLOCK, LDS ? REFILL_WAVES_LDS : (variant_q4(V0) ? REFILL_WAVES_Q4 : REFILL_WAVES)) k_trace_refill(FrameArgs fa, SceneView gsv, PathBuf in, HitBuf hits,
                                                                      const int* cnt, int tail_threshold,
                                                                      unsigned long long* stats, int refill_min, int* work) {
-    // LDS-staged nodes: padded stride; global tables: global node loads (no treelet)
+    // LDS-staged tables: bit 3 (node steps skip the stack-top peek); global tables: global node loads (no treelet)
     constexpr int V = LDS ? kernel_variant(V0, true) : V0;
     __shared__ int stack_mem[LDS_STACK * BLOCK];
     extern __shared__ float4 lds_scene[];
@@ -1578,7 +1593,7 @@ __global__ void __launch_bounds__(BLOCK, LDS ? REFILL_WAVES_LDS : (variant_q4(V0
 template <int V0, bool STATS, bool LDS>
 __global__ void __launch_bounds__(BLOCK, LDS ? REFILL_WAVES_LDS : (variant_ifif(V0) ? SHADOW_IFIF_WAVES : REFILL_WAVES)) k_shadow_refill(SceneView gsv, ShadowBuf sh, float4* L, const int* cnt,
                                                                       unsigned long long* stats, int refill_min, int* work) {
-    // LDS-staged nodes: padded stride; global tables: treelet, except with if-if
+    // LDS-staged tables: bit 3 (node steps skip the stack-top peek); global tables: treelet, except with if-if
     // stepping (the split schedule's scenes), where global node loads beat the
     // treelet's flat loads: soup-1M 32-iteration frame 1179.6 / 1188.1 ->
     // 1154.5 / 1153.5 ms (profiles/r03_ab_treelet_global.log)
@@ -1836,6 +1851,16 @@ struct igx_device {
     int shadow_ifif_opt = -1; // if-if stepping in k_shadow_refill (-1: auto = split-schedule scenes)
     int64_t lds_scene_max = 48 * 1024; // stage traversal tables in LDS when they fit (0 = never)
     size_t lds_scene_bytes = 0;        // bytes staged per block for the current scene (0 = global tables)
+    // k_extend's LDS layout for the current scene (configure_lds, host/lds_plan.h):
+    // option "lds_shading" (-1 auto = LDS_SHADING_AUTO, 0 today's 256-thread
+    // kernel exactly, 1 the wide block with the shading tables staged when it
+    // fits); option "lds_shading_max" caps the staged shading tables' bytes
+    int lds_shading_opt = -1;
+    int64_t lds_shading_max = 48 * 1024;
+    size_t lds_shading_bytes = 0;      // shading-table bytes staged behind the traversal tables (0: not staged)
+    int ext_block = BLOCK;             // threads per block of k_extend (BLOCK_WIDE with the shading tables staged)
+    size_t lds_shading_tab[LDS_TAB_COUNT] = {}; // the current scene's shading tables by LdsPlan table
+    size_t lds_per_block = 64 * 1024;  // device attribute: LDS one workgroup may take
     size_t table_bytes = 0;            // traversal tables (nodes, instances, triangles) of the current scene
     size_t shading_bytes = 0;          // shading tables (entities, vertices, normals, faces, materials, lights)
     int leaf_size = 4;
@@ -2078,10 +2103,13 @@ hipEvent_t slot_event(Slot& s) {
 
 // Grid of a stream kernel: enough blocks for `items`, at most the resident
 // blocks, always a multiple of GRID_QUANTUM (every shard gets the same waves).
-int grid_for(igx_device* dev, long long items, int blocks_per_cu) {
-    const long long q = GRID_QUANTUM;
-    long long need = (items + BLOCK - 1) / BLOCK;
-    long long cap = (long long)dev->num_cus * std::min(blocks_per_cu, MAX_BLOCKS_PER_CU);
+// `block`: the kernel's threads per block (BLOCK, or the wide k_extend's): the
+// quantum is NSH over its waves, and a CU holds 2048 threads of any block
+// size, so no grid has more threads than max_grid's (the spill columns).
+int grid_for(igx_device* dev, long long items, int blocks_per_cu, int block = BLOCK) {
+    const long long q = NSH / (block / 64);
+    long long need = (items + block - 1) / block;
+    long long cap = (long long)dev->num_cus * std::min(blocks_per_cu, MAX_BLOCKS_PER_CU * BLOCK / block);
     long long g = std::min((need + q - 1) / q * q, std::max(q, cap / q * q));
     return (int)std::max(q, g);
 }
@@ -2158,9 +2186,47 @@ inline bool use_shadow_ifif(const igx_device* dev) {
         }                                     \
     } while (0)
 
+// The wide k_extend (BLOCK_WIDE threads, shading tables staged behind the
+// traversal tables): its launch, its resident blocks per CU and the
+// one-time raise of its dynamic-LDS limit (a block above 64 KB needs it).
+template <bool STATS>
+void launch_extend_wide(igx_device* dev, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in, const PathBuf& out,
+                        const KernelCounters& kc, int tail) {
+    const size_t dyn = lds_pad16(dev->lds_scene_bytes) + dev->lds_shading_bytes;
+#define L_EXTW(S) hipLaunchKernelGGL((k_extend<S, STATS, true, BLOCK_WIDE>), dim3(grid), dim3(BLOCK_WIDE), dyn, dev->stream, fa, dev->sv, in, out, s.sh, s.L, kc, tail)
+    IGX_DISPATCH_VARIANT8(dev->variant, L_EXTW);
+#undef L_EXTW
+}
+template <typename K>
+hipError_t raise_dynamic_lds(K kernel, size_t dyn) {
+    // once per kernel instantiation and device (the caller's current one), the
+    // limit only grows.  Every wide instantiation has the same function type K,
+    // so the record is keyed by the kernel's address, not held per K.
+    static std::map<std::pair<const void*, int>, size_t> raised;
+    int d = 0;
+    (void)hipGetDevice(&d);
+    const void* const fn = reinterpret_cast<const void*>(kernel);
+    size_t& have = raised[{fn, d}];
+    if (dyn <= have) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+    if (e == hipSuccess) have = dyn;
+    return e;
+}
+template <bool STATS>
+hipError_t extend_wide_prepare(int v, size_t dyn) {
+#define L_PREP(S) return raise_dynamic_lds(k_extend<S, STATS, true, BLOCK_WIDE>, dyn)
+    IGX_DISPATCH_VARIANT8(v, L_PREP);
+#undef L_PREP
+    return hipSuccess;
+}
+
 template <bool STATS>
 void launch_extend(igx_device* dev, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in, const PathBuf& out,
                    const KernelCounters& kc, int tail) {
+    if (dev->ext_block == BLOCK_WIDE) {
+        launch_extend_wide<STATS>(dev, s, grid, fa, in, out, kc, tail);
+        return;
+    }
     if (dev->lds_scene_bytes) {
 #define L_EXTL(S) hipLaunchKernelGGL((k_extend<S, STATS, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, dev->stream, fa, dev->sv, in, out, s.sh, s.L, kc, tail)
         IGX_DISPATCH_VARIANT8(dev->variant, L_EXTL);
@@ -2256,10 +2322,17 @@ void launch_finish(igx_device* dev, Slot& s, int grid, const FrameArgs& fa, cons
 
 // resident blocks per CU of a kernel (persistent grid sizing)
 template <typename K>
-int resident_blocks(K kernel, size_t dyn_lds = 0) {
+int resident_blocks(K kernel, size_t dyn_lds = 0, int block = BLOCK) {
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, BLOCK, dyn_lds) != hipSuccess || nb < 1) nb = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, dyn_lds) != hipSuccess || nb < 1) nb = 1;
     return nb;
+}
+template <bool STATS>
+int extend_wide_blocks_per_cu(int v, size_t dyn) {
+#define L_RW(S) return resident_blocks(k_extend<S, STATS, true, BLOCK_WIDE>, dyn, BLOCK_WIDE)
+    IGX_DISPATCH_VARIANT8(v, L_RW);
+#undef L_RW
+    return 1;
 }
 #define IGX_RES1(K, V, ...) return lds ? resident_blocks(K<V, __VA_ARGS__, true>, lds) : resident_blocks(K<V, __VA_ARGS__, false>, tree)
 #define IGX_RESIDENT(K, ...)                                         \
@@ -2343,6 +2416,18 @@ int shade_blocks_per_cu(bool full) { return full ? resident_blocks(k_shade<true>
     X void launch_shadow<S>(igx_device*, Slot&, int, const int*, int*, hipStream_t);                                       \
     X int trace_blocks_per_cu<S>(int, size_t, bool);                                                                  \
     X int shadow_blocks_per_cu<S>(int, size_t, bool, size_t);
+#define IGX_EXTEND_WIDE_HELPERS(X, S)                                                                                \
+    X void launch_extend_wide<S>(igx_device*, Slot&, int, const FrameArgs&, const PathBuf&, const PathBuf&,          \
+                                 const KernelCounters&, int);                                                        \
+    X hipError_t extend_wide_prepare<S>(int, size_t);                                                                \
+    X int extend_wide_blocks_per_cu<S>(int, size_t);
+#if IGX_PART == 4
+IGX_EXTEND_WIDE_HELPERS(template, true)
+IGX_EXTEND_WIDE_HELPERS(template, false)
+#else
+IGX_EXTEND_WIDE_HELPERS(extern template, true)
+IGX_EXTEND_WIDE_HELPERS(extern template, false)
+#endif
 #if IGX_PART == 1
 IGX_EXTEND_HELPERS(template, true)
 IGX_EXTEND_HELPERS(template, false)
@@ -2417,6 +2502,52 @@ igx_status drain(igx_device* dev) {
     dev->stats.tail_bounce_rays += tc[0];
     dev->stats.tail_shadow_rays += tc[1];
     return IGX_OK;
+}
+
+// k_extend's LDS layout for the current scene, decided at upload and when an
+// option it depends on changes (plan_lds, host/lds_plan.h): today's
+// BLOCK-thread kernel with the traversal tables staged (or global), or the
+// wide block with the shading tables behind them when all of it fits the
+// device's LDS per workgroup.  "lds_shading" -1 takes LDS_SHADING_AUTO.
+#ifndef LDS_SHADING_AUTO
+#define LDS_SHADING_AUTO 1
+#endif
+// k_extend's static LDS beside the stack: the enclosing boxes and the
+// instrumented build's per-wave class counters (planned for either build)
+constexpr size_t EXTEND_FIXED_LDS = 2 * MAX_ENC_BOXES * sizeof(float4) + BLOCK_WIDE / 64 * 36 * sizeof(unsigned long long);
+void configure_lds(igx_device* dev) {
+    dev->lds_scene_bytes = dev->lds_shading_bytes = 0;
+    dev->ext_block = BLOCK;
+    if (!dev->has_scene) return;
+    LdsPlanInput in;
+    in.traversal_bytes = dev->table_bytes;
+    in.traversal_max = dev->lds_scene_max;
+    for (int k = 0; k < LDS_TAB_COUNT; ++k) in.shading_bytes[k] = dev->lds_shading_tab[k];
+    in.shading_max = dev->lds_shading_max;
+    in.shading_on = dev->lds_shading_opt < 0 ? LDS_SHADING_AUTO != 0 : dev->lds_shading_opt != 0;
+    in.stack_bytes_per_thread = LDS_STACK * sizeof(int);
+    in.fixed_bytes = EXTEND_FIXED_LDS;
+    in.lds_per_block = dev->lds_per_block;
+    LdsPlan p = plan_lds(in);
+    if (p.block_threads == BLOCK_WIDE) {
+        // a block above 64 KB: raise the instantiations' dynamic-LDS limit once;
+        // a refusal keeps today's layout; the text in last_error is advisory
+        // (the call that got here still returns IGX_OK)
+        const size_t dyn = lds_pad16(p.traversal_bytes) + p.shading_bytes;
+        (void)hipSetDevice(dev->hip_device);
+        hipError_t e = extend_wide_prepare<false>(dev->variant, dyn);
+        if (e == hipSuccess) e = extend_wide_prepare<true>(dev->variant, dyn);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            dev->last_error = std::string("lds_shading: the wide k_extend's LDS block was refused (") + hipGetErrorString(e) +
+                              "); keeping the 256-thread layout";
+            p.block_threads = BLOCK;
+            p.shading_bytes = 0;
+        }
+    }
+    dev->lds_scene_bytes = p.traversal_bytes;
+    dev->lds_shading_bytes = p.shading_bytes;
+    dev->ext_block = p.block_threads;
 }
 
 // Treelet size of every global-table kernel: the largest prefix of the hot
@@ -2530,6 +2661,9 @@ extern "C" igx_status igx_create(int hip_device, igx_device** out) {
         dev->num_cus = prop.multiProcessorCount;
         dev->mem_total = prop.totalGlobalMem;
     }
+    int lds_block = 0;
+    if (hipDeviceGetAttribute(&lds_block, hipDeviceAttributeMaxSharedMemoryPerBlock, hip_device) == hipSuccess && lds_block > 0)
+        dev->lds_per_block = (size_t)lds_block;
     if (hipStreamCreateWithFlags(&dev->stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&dev->stream2, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&dev->tail_stream, hipStreamNonBlocking) != hipSuccess ||
@@ -2645,9 +2779,16 @@ extern "C" igx_status igx_set_option(igx_device* dev, const char* key, int64_t v
     }
     else if (k == "lds_scene_max") {
         dev->lds_scene_max = value;
-        size_t b = ((size_t)dev->sv.num_nodes * dev->sv.node_f4 + (size_t)dev->sv.num_inst * 4 +
-                    (size_t)dev->sv.num_tris * 3) * 16; // LDS layout (stage_scene_lds)
-        dev->lds_scene_bytes = dev->has_scene && (int64_t)b <= value ? b : 0;
+        configure_lds(dev);
+    }
+    else if (k == "lds_shading") {
+        if (value < -1 || value > 1) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "lds_shading must be -1 (auto), 0 or 1");
+        dev->lds_shading_opt = (int)value;
+        configure_lds(dev);
+    }
+    else if (k == "lds_shading_max") {
+        dev->lds_shading_max = value;
+        configure_lds(dev);
     }
     else if (k == "full_shading") dev->full_shading_opt = value != 0;
     else if (k == "enclosing") dev->enclosing_opt = value != 0;
@@ -3359,9 +3500,17 @@ extern "C" igx_status igx_upload_scene(igx_device* dev, const igx_scene_desc* de
     sv.num_tris = (int)(tris.size() / 3);
     {
         size_t b = ((size_t)sv.num_nodes * nf4 + (size_t)sv.num_inst * 4 + (size_t)sv.num_tris * 3) * 16;
-        const size_t bl = b; // LDS layout (stage_scene_lds): the same tables back to back
-        dev->lds_scene_bytes = (int64_t)bl <= dev->lds_scene_max ? bl : 0;
-        dev->table_bytes = b;
+        dev->table_bytes = b; // the LDS layout (stage_scene_lds) is the same tables back to back; configure_lds below
+        sv.num_ent = (int)(ent.size() / ENT_STRIDE);
+        sv.num_fsh = (int)(fsh.size() / 3);
+        sv.num_fn = (int)fn_tab.size();
+        sv.num_mats = (int)mats.size();
+        dev->lds_shading_tab[LDS_TAB_ENT] = ent.size() * sizeof(ent[0]);
+        dev->lds_shading_tab[LDS_TAB_FSH] = fsh.size() * sizeof(fsh[0]);
+        dev->lds_shading_tab[LDS_TAB_FN] = fn_tab.size() * sizeof(fn_tab[0]);
+        dev->lds_shading_tab[LDS_TAB_MATS] = mats.size() * sizeof(DevMaterial);
+        dev->lds_shading_tab[LDS_TAB_LIGHTS] = lights.size() * sizeof(lights[0]);
+        dev->lds_shading_tab[LDS_TAB_ENT_ENC] = ent_enc.size() * sizeof(ent_enc[0]);
         dev->shading_bytes = ent.size() * sizeof(ent[0]) + vtx.size() * sizeof(vtx[0]) + nrm.size() * sizeof(nrm[0]) +
                              idx.size() * sizeof(idx[0]) + mats.size() * sizeof(DevMaterial) + lights.size() * sizeof(lights[0]) +
                              fn_tab.size() * sizeof(fn_tab[0]) + fsh.size() * sizeof(fsh[0]);
@@ -3420,6 +3569,7 @@ extern "C" igx_status igx_upload_scene(igx_device* dev, const igx_scene_desc* de
     }
     dev->has_scene = true;
     dev->tree_dirty = true;
+    configure_lds(dev); // after configure_stack: the wide k_extend is prepared for the scene's variant
     return IGX_OK;
 }
 
@@ -3620,7 +3770,7 @@ igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
             S.split = false;
             S.bounce_ev.clear();
             S.launched = 0;
-            r.ext_grid = grid_for(dev, r.n, pl.ext_bpc);
+            r.ext_grid = grid_for(dev, r.n, pl.ext_bpc, dev->ext_block);
             r.sh_grid = grid_for(dev, r.n, pl.sh_bpc);
             r.fin_grid = grid_for(dev, std::min<long long>(r.n, r.tail) * (pl.pairs ? 2 : 1), pl.fin_bpc);
             r.fuse_gen = dev->fuse_generate && r.n > r.tail;
@@ -3675,7 +3825,7 @@ igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
                 // shadow rays): late bounces launch few waves, not a full chip
                 // of waves that find no group (IGX_LIVE_GRID)
                 const long long bound = IGX_LIVE_GRID && b >= 2 ? r.live : r.n;
-                const int ext_grid = IGX_LIVE_GRID ? grid_for(dev, bound, pl.ext_bpc) : r.ext_grid;
+                const int ext_grid = IGX_LIVE_GRID ? grid_for(dev, bound, pl.ext_bpc, dev->ext_block) : r.ext_grid;
                 const int sh_grid = IGX_LIVE_GRID ? grid_for(dev, bound, pl.sh_bpc) : r.sh_grid;
                 if (inst) launch_extend<true>(dev, S, ext_grid, fb, in, out, kc, r.tail);
                 else launch_extend<false>(dev, S, ext_grid, fb, in, out, kc, r.tail);
@@ -4042,8 +4192,11 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
     const int sd = dev->variant;
     const size_t ldsb = dev->lds_scene_bytes;
     if (dev->tree_dirty) configure_treelet(dev);
-    const int ext_bpc = inst ? extend_blocks_per_cu<true>(sd, ldsb, tree_bytes(dev, dev->tree_ext))
-                             : extend_blocks_per_cu<false>(sd, ldsb, tree_bytes(dev, dev->tree_ext));
+    const size_t wide_dyn = lds_pad16(ldsb) + dev->lds_shading_bytes;
+    const int ext_bpc = dev->ext_block == BLOCK_WIDE
+                            ? (inst ? extend_wide_blocks_per_cu<true>(sd, wide_dyn) : extend_wide_blocks_per_cu<false>(sd, wide_dyn))
+                            : (inst ? extend_blocks_per_cu<true>(sd, ldsb, tree_bytes(dev, dev->tree_ext))
+                                    : extend_blocks_per_cu<false>(sd, ldsb, tree_bytes(dev, dev->tree_ext)));
     const bool refill = use_refill(dev);
     const int tr_bpc = inst ? trace_blocks_per_cu<true>(sd, dev->lds_scene_bytes, refill)
                             : trace_blocks_per_cu<false>(sd, dev->lds_scene_bytes, refill);
@@ -4169,7 +4322,7 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
                 }
             }
             if (!IGX_LIVE_GRID) bound = n;
-            const int ext_grid = grid_for(dev, bound, ext_bpc), tr_grid = grid_for(dev, bound, tr_bpc);
+            const int ext_grid = grid_for(dev, bound, ext_bpc, dev->ext_block), tr_grid = grid_for(dev, bound, tr_bpc);
             const int shade_grid = grid_for(dev, bound, shade_bpc), sh_grid = grid_for(dev, bound, sh_bpc);
             PathBuf in = (b & 1) ? S.pb : S.pa, out = (b & 1) ? S.pa : S.pb;
             KernelCounters kc{row(2 * b), row(2 * (b + 1)), row(2 * b + 1), dev->dstats, row(WORK_ROW0 + 4 * b)};
@@ -4435,6 +4588,8 @@ extern "C" igx_status igx_get_stats(igx_device* dev, igx_stats* out) {
     out->bvh_width = dev->bvh_width;
     out->node_bytes = dev->nf4 * 16;
     out->lds_scene_bytes = (int32_t)dev->lds_scene_bytes;
+    out->lds_shading_bytes = (int32_t)dev->lds_shading_bytes;
+    out->extend_block_threads = dev->ext_block;
     if (dev->has_scene && dev->tree_dirty) configure_treelet(dev);
     out->shadow_blocks_per_cu = dev->has_scene ? shadow_blocks_per_cu<false>(dev->variant, dev->lds_scene_bytes, use_refill(dev),
                                                                             tree_bytes(dev, dev->tree_shadow)) : 0;

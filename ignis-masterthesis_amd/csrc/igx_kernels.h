@@ -56,6 +56,9 @@ struct SceneView {
     // per mesh vertex: texture coordinates (as vtx), uploaded only when a
     // material carries a texture (DevMaterial::pad, textured_material)
     const float2* uv;
+    // shading-table sizes, for staging them in LDS (stage_scene_lds): entity
+    // records, fsh face records, fn_tab entries, materials
+    int num_ent, num_fsh, num_fn, num_mats;
 };
 
 // Copy the traversal tables (nodes, instances, triangles) of a small scene
@@ -73,7 +76,15 @@ __device__ __forceinline__ const float4* stage_enc_boxes(const SceneView& sv) {
     return enc_box_lds;
 }
 
-template <int BLOCK_>
+// SHADE: the shading tables a hit reads through dependent, scattered loads
+// (entity record, per-face shading record, face normal, material, light,
+// enclosing index) follow the traversal tables, each 16-B aligned in the
+// order of the host's LdsPlan (host/lds_plan.h); the view then points at the
+// copies, so shade_step and surface_element read the same values from LDS
+// (ds_read).  Only a kernel launched with room for them sets it (the wide
+// k_extend: one block per CU, scenes with fsh and fn_tab).  spheres, uv,
+// vtx / nrm / idx and the light selector's tables stay in global memory.
+template <int BLOCK_, bool SHADE = false>
 __device__ __forceinline__ SceneView stage_scene_lds(const SceneView& sv, float4* lds) {
     const int nf = sv.node_f4, sh = nf == 8 ? 3 : 2, ns = nf; // node stride in LDS (float4)
     const int n4 = sv.num_nodes * ns, i4 = sv.num_inst * 4, t3 = sv.num_tris * 3;
@@ -81,8 +92,31 @@ __device__ __forceinline__ SceneView stage_scene_lds(const SceneView& sv, float4
     for (int k = threadIdx.x; k < i4; k += BLOCK_) lds[n4 + k] = sv.inst[k];
     for (int k = threadIdx.x; k < t3; k += BLOCK_) lds[n4 + i4 + k] = sv.tris[k];
     const float4* eb = stage_enc_boxes<BLOCK_>(sv);
-    __syncthreads();
     SceneView l = sv;
+    if constexpr (SHADE) {
+        constexpr int M4 = sizeof(DevMaterial) / 16, L4 = sizeof(DevLight) / 16;
+        float4* const s_ent = lds + n4 + i4 + t3;
+        float4* const s_fsh = s_ent + sv.num_ent * ENT_STRIDE;
+        float4* const s_fn = s_fsh + sv.num_fsh * 3;
+        float4* const s_mats = s_fn + sv.num_fn;
+        float4* const s_lights = s_mats + sv.num_mats * M4;
+        int* const s_enc = reinterpret_cast<int*>(s_lights + sv.num_lights * L4);
+        const float4* const g_mats = reinterpret_cast<const float4*>(sv.mats);
+        const float4* const g_lights = reinterpret_cast<const float4*>(sv.lights);
+        for (int k = threadIdx.x; k < sv.num_ent * ENT_STRIDE; k += BLOCK_) s_ent[k] = sv.ent[k];
+        for (int k = threadIdx.x; k < sv.num_fsh * 3; k += BLOCK_) s_fsh[k] = sv.fsh[k];
+        for (int k = threadIdx.x; k < sv.num_fn; k += BLOCK_) s_fn[k] = sv.fn_tab[k];
+        for (int k = threadIdx.x; k < sv.num_mats * M4; k += BLOCK_) s_mats[k] = g_mats[k];
+        for (int k = threadIdx.x; k < sv.num_lights * L4; k += BLOCK_) s_lights[k] = g_lights[k];
+        for (int k = threadIdx.x; k < sv.num_ent; k += BLOCK_) s_enc[k] = sv.ent_enc[k];
+        l.ent = s_ent;
+        l.fsh = s_fsh;
+        l.fn_tab = s_fn;
+        l.mats = reinterpret_cast<const DevMaterial*>(s_mats);
+        l.lights = reinterpret_cast<const DevLight*>(s_lights);
+        l.ent_enc = s_enc;
+    }
+    __syncthreads();
     l.enc_box = eb;
     l.nodes = lds;
     l.inst = lds + n4;
@@ -200,7 +234,7 @@ __device__ __forceinline__ bool is_leaf_ref(int r) { return r < 0 && r > REF_EXI
 // no longer scales with the worst-case stack depth.
 // The LDS column stride is the block size, a compile-time constant: a push or
 // pop is then one shift-add, not a quarter-rate v_mul_lo_u32.
-constexpr int TSTACK_STRIDE = 256; // threads per block of every traversal kernel
+constexpr int TSTACK_STRIDE = 256; // threads per stack region: the block of every traversal kernel (the wide k_extend holds four)
 struct TStack {
     int* lds;
     int* spill;
@@ -298,9 +332,16 @@ __device__ __forceinline__ void tpush_hits3(const TStack& s, int& sp, int n, int
     if (n > 2) tpush<SPILL>(s, sp, r2);
     if (n > 1) tpush<SPILL>(s, sp, r1);
 }
+// BT threads per block (a multiple of TSTACK_STRIDE): every TSTACK_STRIDE
+// threads of the block share one region of LDS_STACK x TSTACK_STRIDE entries
+// (the column stride stays TSTACK_STRIDE); the spill column is the grid thread
+template <int BT = TSTACK_STRIDE>
 __device__ __forceinline__ TStack make_tstack(int* lds_base, int cap, int* spill) {
-    const int g = blockIdx.x * TSTACK_STRIDE + threadIdx.x;
-    return TStack{lds_base + threadIdx.x, spill + g, cap, (int)(gridDim.x * TSTACK_STRIDE)};
+    static_assert(BT % TSTACK_STRIDE == 0, "a block is a whole number of stack regions");
+    const int g = blockIdx.x * BT + threadIdx.x;
+    int* col = lds_base + threadIdx.x;
+    if constexpr (BT > TSTACK_STRIDE) col = lds_base + (threadIdx.x / TSTACK_STRIDE) * (LDS_STACK * TSTACK_STRIDE) + threadIdx.x % TSTACK_STRIDE;
+    return TStack{col, spill + g, cap, (int)(gridDim.x * BT)};
 }
 
 // Closest-hit acceptance with an order-independent tie rule: among hits at the
