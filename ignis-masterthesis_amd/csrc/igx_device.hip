@@ -30,6 +30,7 @@
 #include "../host/bvh_build.h"
 #include "../host/light_select.h"
 #include "../host/lds_plan.h"
+#include "../host/aov_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -54,7 +55,8 @@ using namespace igxd;
 // kernel instantiations build in parallel:
 //   0 = host driver, C-ABI and the small kernels; 1 = k_extend variants;
 //   2 = k_finish variants; 3 = k_trace / k_trace_refill / k_shade / k_shadow /
-//   k_shadow_refill variants; 4 = the wide (BLOCK_WIDE-thread) k_extend variants.  Types and device functions are shared; each
+//   k_shadow_refill variants; 4 = the wide (BLOCK_WIDE-thread) k_extend variants;
+//   5 = the k_infobuffer variants.  Types and device functions are shared; each
 //   part instantiates only its own launch helpers (explicit instantiation),
 //   the others see them as extern templates.
 #ifndef IGX_PART
@@ -1728,6 +1730,114 @@ __global__ void __launch_bounds__(BLOCK) k_trace_hits(SceneView sv, const float*
 }
 
 // ---------------------------------------------------------------------------
+// Denoiser feature buffers: the info-buffer technique (technique/infobuffer.art,
+// InfoBufferTechnique.cpp), one extra pass with one sample per pixel that
+// fills the AOVs "Normals", "Albedo" and "Depth" and leaves the film alone
+// (LockFramebuffer, OverrideSPI = 1, InfoBufferTechnique.cpp:37-38).
+//
+// One lane per local pixel, grid-stride; the lane owns its pixel, so it adds
+// to the three row-major RGB films with plain read-modify-writes, the
+// iterations of a multi-iteration call in order inside the lane: no atomics,
+// no per-slot buffers, bit-reproducible.  The camera path is sample 0 of the
+// iteration (gen_path: the same seed and the same two jitter draws as the
+// film's sample 0; in ray-list mode the ray of the list), traced against the
+// global tables with the LDS stack of k_trace_hits.
+// ---------------------------------------------------------------------------
+struct InfoArgs {
+    float* normals; // the three films, fb_width pixels per row
+    float* albedo;
+    float* depth;
+    int fb_width;
+    int mode;            // option "denoise_aovs" (host/aov_plan.h: INFO_FIRST, INFO_EVERY)
+    int follow_specular; // option "denoise_follow_specular" (Denoiser.FollowSpecular)
+    int max_depth;       // option "denoise_max_depth" (__tech_ib_max_depth, LoaderTechnique.cpp:133)
+};
+
+template <int V>
+__global__ void __launch_bounds__(BLOCK) k_infobuffer(FrameArgs fa, SceneView sv, InfoArgs ia) {
+    __shared__ int stack_mem[LDS_STACK * BLOCK];
+    const TStack ts = make_tstack(stack_mem, LDS_STACK, sv.spill);
+    constexpr bool FULL = variant_full(V);
+    TraceStats st{0, 0, 0, 0, 0, 0, 0};
+    const int iters = fa.chunk_iters, iter0 = fa.iter;
+    fa.chunk_iters = 1; // slot lp of `fa` is sample 0 of local pixel lp in iteration fa.iter (spi 1)
+    for (int lp = blockIdx.x * BLOCK + threadIdx.x; lp < fa.chunk_pixels; lp += gridDim.x * BLOCK) {
+        int x, y;
+        if (!local_to_global(fa, lp, x, y)) continue; // tile padding
+        const size_t at = 3 * ((size_t)y * ia.fb_width + x);
+        f3 nsum = mk(ia.normals[at], ia.normals[at + 1], ia.normals[at + 2]);
+        f3 asum = mk(ia.albedo[at], ia.albedo[at + 1], ia.albedo[at + 2]);
+        f3 dsum = mk(ia.depth[at], ia.depth[at + 1], ia.depth[at + 2]);
+        // PixelCoord::linear = y * w + x (driver/camera.art:24); the list emitter's y is 0
+        const uint32_t albedo_seed = hash_combine(0x811C9DC5u, (uint32_t)(y * fa.width + x));
+        for (int k = 0; k < iters; ++k) {
+            if (!info_pass_due(ia.mode, (int64_t)iter0 + k)) continue; // wave-uniform
+            fa.iter = iter0 + k;
+            const GenPath g = gen_path(fa, sv, lp);
+            f3 o = g.o, d = g.d;
+            Rng rnd{g.seed, g.counter};
+            float tmin, tmax;
+            uint32_t rflags;
+            ray_extent(fa, sv, 1, lp, tmin, tmax, rflags);
+            // IBRayPayload (infobuffer.art:4-22): depth from 1, the distance travelled so far
+            float travelled = 0;
+            for (int depth = 1;;) {
+                int hit_ent, hit_prim;
+                float hu = 0, hv = 0;
+                trace_ray<false, false, V>(sv, o, d, tmin, tmax, rflags, ts, hit_ent, hit_prim, hu, hv, st);
+                if (hit_ent < 0) break; // TechniqueNoMissFunction: nothing is written
+                int mat_id;
+                const Surface s = surface_element(sv, hit_ent, hit_prim, tmax, hu, hv, o, d, mat_id);
+                // the material as shade_step fetches it (a texture writes its value into a copy)
+                std::conditional_t<FULL, DevMaterial, const DevMaterial&> m = sv.mats[mat_id];
+                if constexpr (FULL)
+                    if (sv.uv) apply_texture(sv, m, hit_ent, hit_prim, hu, hv);
+                const f3 out_dir = neg(d);
+                if (!(ia.follow_specular && bsdf_is_specular<FULL>(m))) {
+                    // on_hit (infobuffer.art:34-61): the albedo from 16 BSDF samples of a
+                    // generator of the pixel's own, without the cosine term
+                    f3 albedo = mk(0, 0, 0);
+                    Rng arnd{albedo_seed, 1};
+#pragma unroll 1
+                    for (int j = 0; j < 16; ++j) {
+                        const BsdfSample bs = bsdf_sample<FULL>(m, s, arnd, out_dir);
+                        if (bs.valid) {
+                            const float c = absolute_cos(bs.in_dir, s.local.n);
+                            albedo = add(albedo, mulf(bs.color, safe_div(bs.pdf, 16.0f * c)));
+                        }
+                    }
+                    nsum = add(nsum, s.local.n);
+                    asum = add(asum, mk(fminf(albedo.x, 1.0f), fminf(albedo.y, 1.0f), fminf(albedo.z, 1.0f))); // color_saturate(albedo, 1)
+                    const float dist = tmax + (ia.follow_specular ? travelled : 0.0f);
+                    dsum = add(dsum, mk(dist, dist, dist));
+                    break;
+                }
+                // on_bounce (infobuffer.art:63-88): follow the specular surface
+                if (!(depth <= ia.max_depth)) break;
+                const BsdfSample bs = bsdf_sample<FULL>(m, s, rnd, out_dir);
+                if (!bs.valid) break;
+                travelled = travelled + tmax;
+                ++depth;
+                o = s.point;
+                d = bs.in_dir;
+                tmin = 0.001f;
+                tmax = FLT_MAX_;
+                rflags = RAY_BOUNCE;
+            }
+        }
+        ia.normals[at] = nsum.x;
+        ia.normals[at + 1] = nsum.y;
+        ia.normals[at + 2] = nsum.z;
+        ia.albedo[at] = asum.x;
+        ia.albedo[at + 1] = asum.y;
+        ia.albedo[at + 2] = asum.z;
+        ia.depth[at] = dsum.x;
+        ia.depth[at + 1] = dsum.y;
+        ia.depth[at + 2] = dsum.z;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
 // Two stream "slots" (path double-buffer, shadow stream, radiance, counters)
@@ -1947,6 +2057,19 @@ struct igx_device {
     float* aov_fb[2] = {nullptr, nullptr};
     int fb_w = 0, fb_h = 0;
     uint64_t iteration_count = 0;
+    // Denoiser feature buffers "Normals", "Albedo", "Depth" (k_infobuffer),
+    // fb_count floats each, in ray-list mode too; every one with its own
+    // iteration count (Device.cpp:1390-1403, 1468-1471).  Options
+    // "denoise_aovs" (host/aov_plan.h: INFO_OFF, INFO_FIRST, INFO_EVERY),
+    // "denoise_follow_specular", "denoise_max_depth" (LoaderTechnique.cpp:133)
+    int info_mode = INFO_OFF;
+    bool info_follow_specular = false;
+    int info_max_depth = 8;
+    float* info_fb[AOV_INFO_COUNT] = {nullptr, nullptr, nullptr};
+    uint64_t info_count[AOV_INFO_COUNT] = {0, 0, 0};
+    // option "timing": the event pairs around the info-buffer passes queued
+    // since the last drain (folded into ms_generate there)
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> info_timed;
     // stats
     igx_stats stats{};
     // asynchronous rendering (option "async_render"): the worker thread and
@@ -2403,6 +2526,17 @@ void launch_shade(igx_device* dev, bool full, int grid, const FrameArgs& fa, con
 int shade_blocks_per_cu(bool full) { return full ? resident_blocks(k_shade<true>) : resident_blocks(k_shade<false>); }
 #endif
 
+// the info-buffer pass (k_infobuffer) on `strm`, for the scene view `sv` (the
+// caller's copy: its camera and the spill columns of that stream)
+void launch_infobuffer(igx_device* dev, int grid, hipStream_t strm, const FrameArgs& fa, const SceneView& sv, const InfoArgs& ia);
+#if IGX_PART == 5
+void launch_infobuffer(igx_device* dev, int grid, hipStream_t strm, const FrameArgs& fa, const SceneView& sv, const InfoArgs& ia) {
+#define L_IB(S) hipLaunchKernelGGL(k_infobuffer<S>, dim3(grid), dim3(BLOCK), 0, strm, fa, sv, ia)
+    IGX_DISPATCH_VARIANT8(dev->variant, L_IB);
+#undef L_IB
+}
+#endif
+
 // Launch helpers: defined (explicitly instantiated) in their part, extern elsewhere.
 #define IGX_EXTEND_HELPERS(X, S)                                                                                     \
     X void launch_extend<S>(igx_device*, Slot&, int, const FrameArgs&, const PathBuf&, const PathBuf&,               \
@@ -2494,6 +2628,13 @@ igx_status drain(igx_device* dev) {
     HIPCHK(hipStreamSynchronize(dev->stream2));
     HIPCHK(hipStreamSynchronize(dev->shadow_stream));
     HIPCHK(hipStreamSynchronize(dev->tail_stream));
+    for (auto& t : dev->info_timed) { // info-buffer passes (option "timing")
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, t.first, t.second) == hipSuccess) dev->stats.ms_generate += ms;
+        (void)hipEventDestroy(t.first);
+        (void)hipEventDestroy(t.second);
+    }
+    dev->info_timed.clear();
     unsigned long long tc[2] = {0, 0};
     HIPCHK(hipMemcpy(tc, dev->tail_counts, sizeof(tc), hipMemcpyDeviceToHost));
     HIPCHK(hipMemset(dev->tail_counts, 0, sizeof(tc)));
@@ -2702,6 +2843,12 @@ extern "C" igx_status igx_destroy(igx_device* dev) {
     if (dev->fb) (void)hipFree(dev->fb);
     for (float* a : dev->aov_fb)
         if (a) (void)hipFree(a);
+    for (float* a : dev->info_fb)
+        if (a) (void)hipFree(a);
+    for (auto& t : dev->info_timed) {
+        (void)hipEventDestroy(t.first);
+        (void)hipEventDestroy(t.second);
+    }
     if (dev->dstats) (void)hipFree(dev->dstats);
     if (dev->tail_counts) (void)hipFree(dev->tail_counts);
     if (dev->ray_list) (void)hipFree(dev->ray_list);
@@ -2754,6 +2901,16 @@ extern "C" igx_status igx_set_option(igx_device* dev, const char* key, int64_t v
     }
     else if (k == "concurrent_chunks") dev->concurrent_opt = value != 0 ? 1 : 0;
     else if (k == "async_render") dev->async_opt = value != 0 ? 1 : 0;
+    else if (k == "denoise_aovs") {
+        if (value < INFO_OFF || value > INFO_EVERY)
+            return fail(dev, IGX_ERR_INVALID_ARGUMENT, "denoise_aovs must be 0 (off), 1 (first iteration) or 2 (every iteration)");
+        dev->info_mode = (int)value; // the films come and go at the next render
+    }
+    else if (k == "denoise_follow_specular") dev->info_follow_specular = value != 0;
+    else if (k == "denoise_max_depth") {
+        if (value < 0) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "denoise_max_depth must be >= 0");
+        dev->info_max_depth = (int)std::min<int64_t>(value, 1 << 20);
+    }
     else if (k == "probe_sample") dev->probe_sample_opt = std::max<int64_t>(0, value);
     else if (k == "fail_chunk") dev->fail_chunk_opt = std::max<int64_t>(0, value);
     else if (k == "face_shade") dev->face_shade_opt = value != 0 ? 1 : 0;
@@ -3604,8 +3761,23 @@ struct ChunkPlan { // one render call's chunking (render_impl)
     int max_bounces = 1, ext_bpc = 1, sh_bpc = 1, fin_bpc = 1;
     bool pairs = false;
 };
+// One info-buffer pass (k_infobuffer): the iterations of one render call
+struct InfoPass {
+    FrameArgs fa{}; // spi 1, one chunk of every local pixel, chunk_iters = the call's iterations
+    DevCamera cam{};
+    InfoArgs ia{};
+    int grid = 1;
+};
+// What a clear resets (igx_clear: everything; igx_clear_aov: one film):
+// bit 0 the film, bit 1 + k the AOV with index k of host/aov_plan.h
+constexpr uint32_t CLEAR_FILM = 1u, CLEAR_ALL = (2u << AOV_COUNT) - 1u;
+constexpr uint32_t clear_bit(int aov) { return 2u << aov; }
 struct SchedItem {
     bool clear = false;
+    uint32_t clear_mask = CLEAR_ALL;
+    // an info-buffer pass: like a clear, queued on the tail stream in submission order
+    std::shared_ptr<const InfoPass> info;
+    bool fence() const { return clear || info; } // no chunk of its own
     std::shared_ptr<const ChunkPlan> plan;
     int it0 = 0;
     long long px0 = 0;
@@ -3637,16 +3809,22 @@ struct ChunkScheduler {
             }
         if (items.size() > first) items.back().last_of_plan = true;
     }
-    void add_clear() {
+    void add_clear(uint32_t mask) {
         SchedItem s;
         s.clear = true;
+        s.clear_mask = mask;
+        items.push_back(s);
+    }
+    void add_info(const std::shared_ptr<const InfoPass>& pass) {
+        SchedItem s;
+        s.info = pass;
         items.push_back(s);
     }
     igx_status step(igx_device* dev, bool& progress);
     // every chunk has started and is down to concurrent_start_pct % of its paths (or done)
     bool all_late(int pct) const {
         for (const SchedItem& r : items) {
-            if (r.clear) continue;
+            if (r.fence()) continue;
             if (!r.started) return false;
             if (!r.loop_done && r.live * 100 > (long long)pct * r.n) return false;
         }
@@ -3657,7 +3835,13 @@ struct AsyncRender {
     std::thread th;
     std::mutex m;
     std::condition_variable cv, cv_idle;
-    std::deque<std::pair<bool, std::shared_ptr<const ChunkPlan>>> jobs; // (clear, plan)
+    struct Job { // a clear (of `clear_mask`), an info-buffer pass, or a render call's plan
+        bool clear = false;
+        uint32_t clear_mask = CLEAR_ALL;
+        std::shared_ptr<const InfoPass> info;
+        std::shared_ptr<const ChunkPlan> plan;
+    };
+    std::deque<Job> jobs;
     bool stop = false, idle = true;
     bool late = true; // every chunk submitted has started and is in its late bounces (igx_wait_ready)
     // a step failed on the worker: everything queued was dropped, so the film
@@ -3668,6 +3852,37 @@ struct AsyncRender {
     std::string msg;
     ChunkScheduler sched; // the worker's
 };
+
+// Zero the films `mask` names (CLEAR_*), behind the work queued on `strm`.
+static igx_status queue_clear(igx_device* dev, uint32_t mask, hipStream_t strm) {
+    const size_t bytes = dev->fb_count * sizeof(float);
+    if (dev->fb && (mask & CLEAR_FILM)) HIPCHK(hipMemsetAsync(dev->fb, 0, bytes, strm));
+    for (int k = 0; k < AOV_MIS_COUNT; ++k)
+        if (dev->aov_fb[k] && (mask & clear_bit(AOV_MIS_FIRST + k))) HIPCHK(hipMemsetAsync(dev->aov_fb[k], 0, bytes, strm));
+    for (int k = 0; k < AOV_INFO_COUNT; ++k)
+        if (dev->info_fb[k] && (mask & clear_bit(AOV_INFO_FIRST + k))) HIPCHK(hipMemsetAsync(dev->info_fb[k], 0, bytes, strm));
+    return IGX_OK;
+}
+
+// Launch an info-buffer pass on `strm`, whose spill columns are `spill`.
+static igx_status queue_info_pass(igx_device* dev, const InfoPass& ps, hipStream_t strm, int* spill) {
+    SceneView sv = dev->sv;
+    sv.cam = ps.cam;
+    sv.spill = spill;
+    hipEvent_t a = nullptr, b = nullptr;
+    if (dev->timing) {
+        HIPCHK(hipEventCreate(&a));
+        HIPCHK(hipEventCreate(&b));
+        HIPCHK(hipEventRecord(a, strm));
+    }
+    launch_infobuffer(dev, ps.grid, strm, ps.fa, sv, ps.ia);
+    HIPCHK(hipGetLastError());
+    if (b) {
+        HIPCHK(hipEventRecord(b, strm));
+        dev->info_timed.push_back({a, b});
+    }
+    return IGX_OK;
+}
 
 igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
     hipStream_t const main0 = dev->stream, tail0 = dev->tail_stream;
@@ -3715,7 +3930,7 @@ igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
     SchedItem* nx = nullptr;
     bool late = true;
     for (SchedItem& r : items) {
-        if (r.clear) continue;
+        if (r.fence()) continue;
         if (!r.started) {
             nx = &r;
             break;
@@ -3726,7 +3941,7 @@ igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
         const int k = dev->stream_slots == 1 ? 0 : dev->next_slot;
         Slot& S = dev->slots[k];
         bool busy = false;
-        for (const SchedItem& r : items) busy = busy || (!r.clear && r.started && r.slot == k);
+        for (const SchedItem& r : items) busy = busy || (!r.fence() && r.started && r.slot == k);
         if (!busy && S.pending) {
             const hipError_t q = hipEventQuery(S.done);
             if (q == hipErrorNotReady) busy = true;
@@ -3794,7 +4009,7 @@ igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
     }
     // advance every chunk's bounce loop as far as its lagged counts allow
     for (SchedItem& r : items) {
-        if (r.clear || !r.started || r.tail_queued) continue;
+        if (r.fence() || !r.started || r.tail_queued) continue;
         Slot& S = dev->slots[r.slot];
         const ChunkPlan& pl = *r.plan;
         const int max_bounces = pl.max_bounces;
@@ -3876,13 +4091,12 @@ igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
         }
         restore();
     }
-    // resolves and framebuffer clears strictly in submission order on the tail stream
-    while (!items.empty() && (items.front().clear || items.front().tail_queued)) {
+    // resolves, framebuffer clears and info-buffer passes strictly in submission order on the tail stream
+    while (!items.empty() && (items.front().fence() || items.front().tail_queued)) {
         SchedItem& r = items.front();
-        if (r.clear) {
-            IGX_CC(hipMemsetAsync(dev->fb, 0, dev->fb_count * sizeof(float), tail0));
-            for (float* a : dev->aov_fb)
-                if (a) IGX_CC(hipMemsetAsync(a, 0, dev->fb_count * sizeof(float), tail0));
+        if (r.fence()) {
+            const igx_status st = r.clear ? queue_clear(dev, r.clear_mask, tail0) : queue_info_pass(dev, *r.info, tail0, spill_tail0);
+            if (st != IGX_OK) return st;
         } else {
             Slot& S = dev->slots[r.slot];
             IGX_CC(hipStreamWaitEvent(tail0, r.fin_ev, 0));
@@ -3946,8 +4160,10 @@ static void async_worker(igx_device* dev) {
         {
             std::unique_lock<std::mutex> lk(a.m);
             while (!a.jobs.empty()) {
-                if (a.jobs.front().first) a.sched.add_clear();
-                else a.sched.add(a.jobs.front().second);
+                const AsyncRender::Job& j = a.jobs.front();
+                if (j.clear) a.sched.add_clear(j.clear_mask);
+                else if (j.info) a.sched.add_info(j.info);
+                else a.sched.add(j.plan);
                 a.jobs.pop_front();
             }
             if (a.sched.empty()) {
@@ -4038,14 +4254,14 @@ void stop_async(igx_device* dev) {
     dev->async = nullptr;
 }
 
-static void submit_async(igx_device* dev, bool clear, std::shared_ptr<const ChunkPlan> plan) {
+static void submit_async(igx_device* dev, AsyncRender::Job job) {
     if (!dev->async) {
         dev->async = new AsyncRender();
         dev->async->th = std::thread(async_worker, dev);
     }
     {
         std::lock_guard<std::mutex> lk(dev->async->m);
-        dev->async->jobs.push_back({clear, std::move(plan)});
+        dev->async->jobs.push_back(std::move(job));
         dev->async->idle = false;
         dev->async->late = false;
     }
@@ -4090,7 +4306,24 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
     // framebuffer (resize clears, as Device::resize)
     size_t fbc = (size_t)width * height * 3;
     const bool want_aov = dev->aov_on && !list_mode;
-    if (dev->fb_w != width || dev->fb_h != height || !dev->fb || want_aov != (dev->aov_fb[0] != nullptr)) {
+    const bool resize = dev->fb_w != width || dev->fb_h != height || !dev->fb || want_aov != (dev->aov_fb[0] != nullptr);
+    // the denoiser's three films come and go with option "denoise_aovs"; a
+    // resize clears them (and their counts) with the film
+    const bool want_info = dev->info_mode != INFO_OFF;
+    if (resize || want_info != (dev->info_fb[0] != nullptr)) {
+        igx_status dst = drain(dev);
+        if (dst != IGX_OK) return dst;
+        for (int k = 0; k < AOV_INFO_COUNT; ++k) {
+            if (dev->info_fb[k]) HIPCHK(hipFree(dev->info_fb[k]));
+            dev->info_fb[k] = nullptr;
+            dev->info_count[k] = 0;
+            if (want_info) {
+                HIPCHK(hipMalloc((void**)&dev->info_fb[k], fbc * sizeof(float)));
+                HIPCHK(hipMemsetAsync(dev->info_fb[k], 0, fbc * sizeof(float), dev->tail_stream));
+            }
+        }
+    }
+    if (resize) {
         igx_status dst = drain(dev);
         if (dst != IGX_OK) return dst;
         if (dev->fb) HIPCHK(hipFree(dev->fb));
@@ -4155,6 +4388,35 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
         local_pixels = (long long)width * height;
     }
     // capacity: whole iteration resident when it fits (<= 16M paths), pixel aligned
+    // The denoiser's info-buffer pass of the iterations that get one
+    // (InfoBufferTechnique.cpp:56-66), ahead of their chunks as the reference
+    // injects it: one launch, queued in call order where clears and resolves
+    // are (the tail stream; with async_render by the worker, like a clear).
+    if (const int64_t passes = info_passes_in(dev->info_mode, p->iteration, count); passes > 0 && dev->info_fb[0]) {
+        for (uint64_t& c : dev->info_count) c += (uint64_t)passes;
+        if (local_pixels > 0) {
+            auto pass = std::make_shared<InfoPass>();
+            pass->fa = fa;
+            pass->fa.spi = 1;
+            pass->fa.inv_spi = 1.0f;
+            pass->fa.probe_sample = 0;
+            pass->fa.chunk_pixel0 = 0;
+            pass->fa.chunk_pixels = (int)local_pixels;
+            pass->fa.chunk_iters = count;
+            pass->cam = cam;
+            pass->ia = InfoArgs{dev->info_fb[0], dev->info_fb[1], dev->info_fb[2], width,
+                                dev->info_mode,  dev->info_follow_specular ? 1 : 0, dev->info_max_depth};
+            pass->grid = grid_for(dev, local_pixels, MAX_BLOCKS_PER_CU);
+            if (async) {
+                AsyncRender::Job job;
+                job.info = std::move(pass);
+                submit_async(dev, std::move(job));
+            } else {
+                igx_status st = queue_info_pass(dev, *pass, dev->tail_stream, dev->spill_tail);
+                if (st != IGX_OK) return st;
+            }
+        }
+    }
     long long total_paths = local_pixels * p->spi;
     if (total_paths == 0) {
         dev->iteration_count += count;
@@ -4227,7 +4489,9 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
         dev->iteration_count += count;
         dev->stats.iterations += count;
         if (async) {
-            submit_async(dev, false, std::move(plan));
+            AsyncRender::Job job;
+            job.plan = std::move(plan);
+            submit_async(dev, std::move(job));
         } else {
             ChunkScheduler sched;
             sched.add(plan);
@@ -4439,22 +4703,23 @@ extern "C" igx_status igx_get_framebuffer(igx_device* dev, float* host_rgb, size
 // "Color" (or "" / NULL) is the film; "Direct Weights" and "NEE Weights" exist
 // with the technique's aov_mis (PathTechnique.cpp:23-27); any other name is an
 // unknown AOV (the reference logs it and returns no data)
-static int aov_index(igx_device* dev, const char* name) {
-    const std::string n = name ? name : "";
-    if (n.empty() || n == "Color") return -1;
-    if (dev->aov_on && n == "Direct Weights") return 0;
-    if (dev->aov_on && n == "NEE Weights") return 1;
-    return -2;
-}
+// and with the denoiser (option "denoise_aovs") "Normals", "Albedo" and "Depth"
+// (InfoBufferTechnique.cpp:28-30).  The table: host/aov_plan.h.
+static int aov_index(igx_device* dev, const char* name) { return aov_lookup(name, dev->aov_on, dev->info_mode != INFO_OFF); }
+// the film of AOV k >= 0 (nullptr before the first render with it) and its
+// iteration count: the info AOVs count their own passes, the MIS AOVs
+// accumulate with the film
+static float* aov_film(igx_device* dev, int k) { return k >= AOV_INFO_FIRST ? dev->info_fb[k - AOV_INFO_FIRST] : dev->aov_fb[k]; }
+static uint64_t aov_count(igx_device* dev, int k) { return k >= AOV_INFO_FIRST ? dev->info_count[k - AOV_INFO_FIRST] : dev->iteration_count; }
 
 extern "C" igx_status igx_get_aov(igx_device* dev, const char* name, float* host_rgb, size_t count, uint64_t* iteration_count) {
     if (!dev) return IGX_ERR_INVALID_ARGUMENT;
     const int k = aov_index(dev, name);
     if (k == -1) return igx_get_framebuffer(dev, host_rgb, count, iteration_count);
     if (k == -2) return fail(dev, IGX_ERR_INVALID_ARGUMENT, std::string("unknown aov '") + (name ? name : "") + "'");
-    if (iteration_count) *iteration_count = dev->iteration_count;
+    if (iteration_count) *iteration_count = aov_count(dev, k);
     if (!host_rgb) return IGX_OK;
-    if (!dev->aov_fb[k]) {
+    if (!aov_film(dev, k)) {
         std::memset(host_rgb, 0, count * sizeof(float));
         return IGX_OK;
     }
@@ -4462,7 +4727,7 @@ extern "C" igx_status igx_get_aov(igx_device* dev, const char* name, float* host
     HIPCHK(hipSetDevice(dev->hip_device));
     igx_status st = drain(dev);
     if (st != IGX_OK) return st;
-    HIPCHK(hipMemcpy(host_rgb, dev->aov_fb[k], count * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(host_rgb, aov_film(dev, k), count * sizeof(float), hipMemcpyDeviceToHost));
     return IGX_OK;
 }
 
@@ -4471,8 +4736,16 @@ extern "C" igx_status igx_aov_device_ptr(igx_device* dev, const char* name, floa
     const int k = aov_index(dev, name);
     if (k == -1) return igx_framebuffer_device_ptr(dev, ptr, count);
     if (k == -2) return fail(dev, IGX_ERR_INVALID_ARGUMENT, std::string("unknown aov '") + (name ? name : "") + "'");
-    *ptr = dev->aov_fb[k];
-    if (count) *count = dev->aov_fb[k] ? dev->fb_count : 0;
+    *ptr = aov_film(dev, k);
+    if (count) *count = *ptr ? dev->fb_count : 0;
+    return IGX_OK;
+}
+
+extern "C" igx_status igx_aov_iteration_count(igx_device* dev, const char* name, uint64_t* iteration_count) {
+    if (!dev || !iteration_count) return IGX_ERR_INVALID_ARGUMENT;
+    const int k = aov_index(dev, name);
+    if (k == AOV_UNKNOWN) return fail(dev, IGX_ERR_INVALID_ARGUMENT, std::string("unknown aov '") + (name ? name : "") + "'");
+    *iteration_count = k == AOV_COLOR ? dev->iteration_count : aov_count(dev, k);
     return IGX_OK;
 }
 
@@ -4512,8 +4785,14 @@ extern "C" igx_status igx_pack_tiles(igx_device* dev, const igx_render_params* p
     return IGX_OK;
 }
 
-extern "C" igx_status igx_clear(igx_device* dev) {
-    if (!dev) return IGX_ERR_INVALID_ARGUMENT;
+// Clears the films of `mask` (CLEAR_*) and their iteration counts: queued
+// behind the renders submitted so far, like them without waiting.
+static igx_status clear_impl(igx_device* dev, uint32_t mask) {
+    auto reset_counts = [&]() {
+        if (mask & CLEAR_FILM) dev->iteration_count = 0;
+        for (int k = 0; k < AOV_INFO_COUNT; ++k)
+            if (mask & clear_bit(AOV_INFO_FIRST + k)) dev->info_count[k] = 0;
+    };
     bool failed = false;
     if (dev->async) {
         {
@@ -4521,11 +4800,21 @@ extern "C" igx_status igx_clear(igx_device* dev) {
             failed = dev->async->err != IGX_OK;
         }
         if (!failed) { // ordered behind the queued renders' resolves by the worker
-            submit_async(dev, true, nullptr);
-            dev->iteration_count = 0;
+            AsyncRender::Job job;
+            job.clear = true;
+            job.clear_mask = mask;
+            submit_async(dev, std::move(job));
+            reset_counts();
             return IGX_OK;
         }
-        // a failed handle: the worker dropped its queue; clear here and lift the failure
+        // a failed handle: the worker dropped its queue; clear here and lift the
+        // failure (only a clear of everything does: one film's clear leaves the
+        // others out of step with their counts, so it reports the failure)
+        if (mask != CLEAR_ALL) {
+            std::lock_guard<std::mutex> lk(dev->async->m);
+            dev->last_error = dev->async->msg;
+            return dev->async->err;
+        }
         reset_async_failure(dev);
         igx_status st = drain(dev);
         if (st != IGX_OK) return st;
@@ -4533,12 +4822,23 @@ extern "C" igx_status igx_clear(igx_device* dev) {
     if (dev->fb) {
         HIPCHK(hipSetDevice(dev->hip_device));
         // resolves of queued chunks land on the tail stream; clear behind them
-        HIPCHK(hipMemsetAsync(dev->fb, 0, dev->fb_count * sizeof(float), dev->tail_stream));
-        for (float* a : dev->aov_fb)
-            if (a) HIPCHK(hipMemsetAsync(a, 0, dev->fb_count * sizeof(float), dev->tail_stream));
+        igx_status st = queue_clear(dev, mask, dev->tail_stream);
+        if (st != IGX_OK) return st;
     }
-    dev->iteration_count = 0;
+    reset_counts();
     return IGX_OK;
+}
+
+extern "C" igx_status igx_clear(igx_device* dev) {
+    if (!dev) return IGX_ERR_INVALID_ARGUMENT;
+    return clear_impl(dev, CLEAR_ALL);
+}
+
+extern "C" igx_status igx_clear_aov(igx_device* dev, const char* name) {
+    if (!dev) return IGX_ERR_INVALID_ARGUMENT;
+    const int k = aov_index(dev, name);
+    if (k == AOV_UNKNOWN) return fail(dev, IGX_ERR_INVALID_ARGUMENT, std::string("unknown aov '") + (name ? name : "") + "'");
+    return clear_impl(dev, k == AOV_COLOR ? CLEAR_FILM : clear_bit(k));
 }
 
 extern "C" igx_status igx_get_stats(igx_device* dev, igx_stats* out) {

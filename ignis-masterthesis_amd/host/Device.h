@@ -313,8 +313,29 @@ public:
     size_t framebufferHeight() const { return mHeight; }
     bool isInteractive() const { return mSettings.IsInteractive; }
 
+    // RuntimeOptions::Denoiser (RuntimeSettings.h:8-9) as the device sees it:
+    // Enabled adds one info-buffer pass (technique/infobuffer.art) to the
+    // first iteration, or to every one, which fills the AOVs "Normals",
+    // "Albedo" and "Depth"; MaxDepth is the loader's __tech_ib_max_depth
+    // (LoaderTechnique.cpp:133).  Takes effect at the next render.
+    struct DenoiserSettings {
+        bool Enabled = false;
+        bool FollowSpecular = false;
+        bool OnlyFirstIteration = true;
+        int MaxDepth = 8;
+    };
+    void setDenoiser(const DenoiserSettings& d) {
+        check(igx_set_option(mDev, "denoise_aovs", d.Enabled ? (d.OnlyFirstIteration ? 1 : 2) : 0));
+        check(igx_set_option(mDev, "denoise_follow_specular", d.FollowSpecular ? 1 : 0));
+        check(igx_set_option(mDev, "denoise_max_depth", d.MaxDepth));
+        mDenoiser = d;
+    }
+    const DenoiserSettings& denoiser() const { return mDenoiser; }
+
     // the film ("" / "Color") or a named AOV of the technique ("Direct Weights",
-    // "NEE Weights" with aov_mis); an unknown name gives {nullptr, 0}, as the
+    // "NEE Weights" with aov_mis; "Normals", "Albedo", "Depth" with the denoiser
+    // enabled, each with an iteration count of its own, Device.cpp:1390-1403);
+    // an unknown name gives {nullptr, 0}, as the
     // reference's getAOVImageForHost / ForDevice (Device.cpp:1330-1388).  Every
     // other failure (a HIP error, a failed asynchronous render) throws: the
     // name is resolved first (igx_aov_device_ptr needs no GPU work), so only
@@ -334,10 +355,18 @@ public:
         uint64_t iters = 0;
         check(igx_synchronize(mDev));
         check(igx_aov_device_ptr(mDev, name.c_str(), &ptr, &n));
-        check(igx_get_framebuffer(mDev, nullptr, 0, &iters));
+        check(igx_aov_iteration_count(mDev, name.c_str(), &iters));
         return AOVAccessor{ptr, (size_t)iters};
     }
-    void clearFramebuffer(const std::string& = "") { check(igx_clear(mDev)); }
+    // Device::clearFramebuffer(name) (Device.cpp:1415-1443): the film ("" /
+    // "Color") or one AOV, with its iteration count; an unknown name is logged
+    void clearFramebuffer(const std::string& name = "") {
+        if (!knownAOV(name)) {
+            std::fprintf(stderr, "igx: clearFramebuffer: unknown aov '%s'\n", name.c_str());
+            return;
+        }
+        check(igx_clear_aov(mDev, name.c_str()));
+    }
     void clearAllFramebuffer() { check(igx_clear(mDev)); }
 
     const Statistics* getStatistics() {
@@ -380,9 +409,11 @@ public:
     igx_device* handle() { return mDev; }
 
 private:
-    // "" / "Color", and the MIS AOVs when the uploaded technique has them
+    // "" / "Color", the MIS AOVs when the uploaded technique has them, and the
+    // denoiser's feature buffers when it is enabled
     bool knownAOV(const std::string& name) const {
         if (name.empty() || name == "Color") return true;
+        if (mDenoiser.Enabled && (name == "Normals" || name == "Albedo" || name == "Depth")) return true;
         return mLast.valid && mLast.technique.aov_mis && (name == "Direct Weights" || name == "NEE Weights");
     }
     void check(igx_status s) {
@@ -432,6 +463,7 @@ private:
     igx_scene* mUploaded = nullptr;
     ShadingCopy mLast;
     igx_camera mCamera{};
+    DenoiserSettings mDenoiser;
     size_t mWidth = 0, mHeight = 0;
     std::unordered_map<std::string, std::vector<float>> mHostFB; // per AOV name
     Statistics mStats;

@@ -10,6 +10,7 @@
 // alphabetical channel order (A, B, G, R), each as width float32 values.
 #include "igx_scene.h"
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -33,24 +34,26 @@ void attr(std::vector<uint8_t>& b, const char* name, const char* type, const std
     b.insert(b.end(), value.begin(), value.end());
 }
 
-} // namespace
+// One channel of the file: its name and where its samples come from (a
+// constant when src is null).
+struct Channel {
+    std::string name;
+    const float* src; // sample (x, y) at src[(y * width + x) * stride]
+    size_t stride;
+    float scale;
+    float constant;
+};
 
-extern "C" int igx_write_exr(const char* path, const float* rgb, int32_t width, int32_t height, int32_t channels, float scale) {
-    if (!path || !rgb || width <= 0 || height <= 0 || (channels != 3 && channels != 4)) return -1;
-    static const char* names4[] = {"A", "B", "G", "R"};
-    static const char* names3[] = {"B", "G", "R"};
-    const char** names = channels == 4 ? names4 : names3;
-    auto src_channel = [&](int k) { // alphabetical position -> interleaved RGB(A) index
-        const char* n = names[k];
-        return n[0] == 'R' ? 0 : n[0] == 'G' ? 1 : n[0] == 'B' ? 2 : 3;
-    };
+// Writes `chans`, already in the alphabetical order the format asks for.
+int write_channels(const char* path, const std::vector<Channel>& chans, int32_t width, int32_t height) {
+    const int channels = (int)chans.size();
     std::vector<uint8_t> hdr;
     put<uint32_t>(hdr, 20000630u);
     put<uint32_t>(hdr, 2u);
     {
         std::vector<uint8_t> v;
         for (int k = 0; k < channels; ++k) {
-            put_str(v, names[k]);
+            put_str(v, chans[k].name.c_str());
             put<int32_t>(v, 2); // FLOAT
             put<uint8_t>(v, 0); // pLinear
             put<uint8_t>(v, 0);
@@ -103,9 +106,9 @@ extern "C" int igx_write_exr(const char* path, const float* rgb, int32_t width, 
     std::vector<float> line((size_t)width * channels);
     for (int32_t y = 0; y < height && ok; ++y) {
         for (int k = 0; k < channels; ++k) {
-            const int c = src_channel(k);
+            const Channel& c = chans[k];
             for (int32_t x = 0; x < width; ++x) {
-                float v = c < 3 ? rgb[((size_t)y * width + x) * 3 + c] * scale : 1.0f;
+                float v = c.src ? c.src[((size_t)y * width + x) * c.stride] * c.scale : c.constant;
                 line[(size_t)k * width + x] = v;
             }
         }
@@ -115,4 +118,35 @@ extern "C" int igx_write_exr(const char* path, const float* rgb, int32_t width, 
     }
     ok = (std::fclose(f) == 0) && ok;
     return ok ? 0 : -3;
+}
+
+} // namespace
+
+extern "C" int igx_write_exr(const char* path, const float* rgb, int32_t width, int32_t height, int32_t channels, float scale) {
+    if (!path || !rgb || width <= 0 || height <= 0 || (channels != 3 && channels != 4)) return -1;
+    std::vector<Channel> chans; // alphabetical: (A,) B, G, R
+    if (channels == 4) chans.push_back({"A", nullptr, 0, 0.0f, 1.0f});
+    chans.push_back({"B", rgb + 2, 3, scale, 0.0f});
+    chans.push_back({"G", rgb + 1, 3, scale, 0.0f});
+    chans.push_back({"R", rgb + 0, 3, scale, 0.0f});
+    return write_channels(path, chans, width, height);
+}
+
+// One file with the channels <name>.R / .G / .B of every layer, the
+// reference's layout for a render with AOVs (frontend/common/IO.cpp:105-129:
+// the film is the layer "Default"); layer k is planes_rgb[k] (row-major RGB)
+// times scales[k].
+extern "C" int igx_write_exr_layers(const char* path, const char* const* names, const float* const* planes_rgb, int32_t n_layers,
+                                    int32_t width, int32_t height, const float* scales) {
+    if (!path || !names || !planes_rgb || !scales || n_layers <= 0 || width <= 0 || height <= 0) return -1;
+    std::vector<Channel> chans;
+    for (int32_t k = 0; k < n_layers; ++k) {
+        if (!names[k] || !*names[k] || !planes_rgb[k]) return -1;
+        static const char* comp[3] = {"R", "G", "B"};
+        for (int c = 0; c < 3; ++c) chans.push_back({std::string(names[k]) + "." + comp[c], planes_rgb[k] + c, 3, scales[k], 0.0f});
+    }
+    std::sort(chans.begin(), chans.end(), [](const Channel& a, const Channel& b) { return a.name < b.name; });
+    for (size_t k = 1; k < chans.size(); ++k)
+        if (chans[k].name == chans[k - 1].name) return -1; // a layer named twice
+    return write_channels(path, chans, width, height);
 }

@@ -11,7 +11,13 @@
 // (main.cpp:103-107, Runtime.cpp:703-708): as the __camera_* vector
 // parameters of render's ParameterSet.  --width / --height override the film
 // (ProgramOptions.cpp:135-139).  --stats prints Statistics::dump's quantities
-// (main.cpp:155-166).  Options of the reference's other targets and of its
+// (main.cpp:155-166).  --denoise-aovs enables the denoiser's feature buffers
+// (RuntimeOptions::Denoiser without the denoiser network itself): the info-buffer
+// pass fills "Normals", "Albedo" and "Depth" in the first iteration, or in every
+// one with --denoiser-aov-every-iteration; --denoiser-follow-specular as the
+// reference's flag (ProgramOptions.cpp:211-213); -o then writes one EXR with
+// the layers Default / Normals / Albedo / Depth, each over its own iteration
+// count (frontend/common/IO.cpp:72-129).  Options of the reference's other targets and of its
 // shader compiler are refused with a message.
 #include "Device.h"
 #include "igx_scene.h"
@@ -28,6 +34,7 @@ static void usage() {
     std::fprintf(stderr,
                  "usage: igcli SCENE.json [--spp N | --time SECONDS] [--spi N] [--seed N] [--gpu] [--gpu-device N]\n"
                  "             [--width W --height H] [--eye X Y Z] [--dir X Y Z] [--up X Y Z] [--stats]\n"
+                 "             [--denoise-aovs [--denoiser-aov-every-iteration] [--denoiser-follow-specular]]\n"
                  "             [-o out.exr|out.pfm]\n");
 }
 
@@ -36,6 +43,7 @@ int main(int argc, char** argv) {
     int spp = 0, spi = 8, seed = 0, device = 0, width = 0, height = 0;
     double render_time = 0; // --time: seconds of rendering instead of a sample count
     bool stats = false;
+    IG::Device::DenoiserSettings denoiser;
     IG::ParameterSet params; // the camera orientation overrides (__camera_eye / _dir / _up)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -64,6 +72,11 @@ int main(int argc, char** argv) {
         else if (a == "--dir") vec3("__camera_dir");
         else if (a == "--up") vec3("__camera_up");
         else if (a == "--stats" || a == "--stats-full") stats = true;
+        else if (a == "--denoise-aovs") denoiser.Enabled = true;
+        else if (a == "--denoiser-aov-every-iteration") denoiser.OnlyFirstIteration = false;
+        else if (a == "--denoiser-aov-first-iteration") denoiser.OnlyFirstIteration = true;
+        else if (a == "--denoiser-follow-specular") denoiser.FollowSpecular = true;
+        else if (a == "--denoiser-skip-specular") denoiser.FollowSpecular = false;
         else if (a == "-o" || a == "--output") out_path = next();
         else if (a == "--gpu" || a == "--no-progress" || a == "--no-color" || a == "-q" || a == "--quiet") {}
         else if (a == "--cpu" || a == "--cpu-arch" || a == "--cpu-threads" || a == "--cpu-vectorwidth") {
@@ -100,6 +113,7 @@ int main(int argc, char** argv) {
         ss.target = IG::Target::makeGPU(device);
         ss.AcquireStats = stats;
         IG::Device dev(ss);
+        if (denoiser.Enabled) dev.setDenoiser(denoiser);
         IG::Device::SceneSettings sc;
         sc.database = &db;
         dev.assignScene(sc);
@@ -136,7 +150,21 @@ int main(int argc, char** argv) {
             IG::Device::AOVAccessor acc = dev.getFramebufferForHost("");
             float inv = acc.IterationCount ? 1.0f / acc.IterationCount : 0.0f;
             const bool pfm = out_path.size() >= 4 && out_path.compare(out_path.size() - 4, 4, ".pfm") == 0;
-            if (!pfm) {
+            if (!pfm && denoiser.Enabled) {
+                // the film as "Default" and the three AOVs, each over its own count (IO.cpp:72-129)
+                const char* names[4] = {"Default", "Normals", "Albedo", "Depth"};
+                const float* planes[4] = {acc.Data, nullptr, nullptr, nullptr};
+                float scales[4] = {inv, 0, 0, 0};
+                for (int k = 1; k < 4; ++k) {
+                    IG::Device::AOVAccessor aov = dev.getFramebufferForHost(names[k]);
+                    planes[k] = aov.Data;
+                    scales[k] = aov.IterationCount ? 1.0f / aov.IterationCount : 0.0f;
+                }
+                if (igx_write_exr_layers(out_path.c_str(), names, planes, 4, W, H, scales) != 0) {
+                    std::fprintf(stderr, "cannot write %s\n", out_path.c_str());
+                    return 1;
+                }
+            } else if (!pfm) {
                 if (igx_write_exr(out_path.c_str(), acc.Data, W, H, 3, inv) != 0) {
                     std::fprintf(stderr, "cannot write %s\n", out_path.c_str());
                     return 1;

@@ -23,7 +23,7 @@ import numpy as np
 from . import _native
 from ._native import EXPORTED_SYMBOLS, LIB_PATH, RenderParams, Stats, lib
 
-__all__ = ["RuntimeOptions", "Scene", "Runtime", "loadFromFile", "loadFromString", "version",
+__all__ = ["RuntimeOptions", "DenoiserSettings", "Scene", "Runtime", "loadFromFile", "loadFromString", "version",
            "EXPORTED_SYMBOLS", "LIB_PATH", "IgxError"]
 
 
@@ -46,6 +46,25 @@ def write_exr(path, rgb, scale=1.0, alpha=False):
         raise IgxError(f"cannot write EXR {path} (code {rc})")
 
 
+def write_exr_layers(path, layers, scales=None):
+    """One EXR with the channels <name>.R / .G / .B of every layer, the
+    reference's layout of a render with AOVs (frontend/common/IO.cpp:105-129;
+    the film is the layer "Default").  `layers`: {name: (H, W, 3) image},
+    `scales`: {name: factor} (e.g. 1 / the layer's own iteration count)."""
+    names = list(layers)
+    imgs = [np.ascontiguousarray(layers[n], dtype=np.float32) for n in names]
+    h, w = imgs[0].shape[0], imgs[0].shape[1]
+    if any(i.shape != (h, w, 3) for i in imgs):
+        raise IgxError("write_exr_layers: every layer must be (H, W, 3) of one size")
+    n = len(names)
+    c_names = (C.c_char_p * n)(*[s.encode() for s in names])
+    c_planes = (C.POINTER(C.c_float) * n)(*[i.ctypes.data_as(C.POINTER(C.c_float)) for i in imgs])
+    c_scales = (C.c_float * n)(*[float((scales or {}).get(s, 1.0)) for s in names])
+    rc = _native.lib().igx_write_exr_layers(os.fsencode(path), c_names, c_planes, n, w, h, c_scales)
+    if rc != 0:
+        raise IgxError(f"cannot write EXR {path} (code {rc})")
+
+
 def recommend_spi(width, height, interactive=False):
     """Runtime.cpp:61-69 for a GPU target."""
     spi_f = 8
@@ -55,10 +74,22 @@ def recommend_spi(width, height, interactive=False):
     return max(1, min(64, spi))
 
 
+class DenoiserSettings:
+    """RuntimeOptions::Denoiser (src/runtime/RuntimeSettings.h:8-9): Enabled adds
+    the info-buffer pass (technique/infobuffer.art) that fills the AOVs
+    "Normals", "Albedo" and "Depth", in the first iteration only or in every one."""
+
+    def __init__(self):
+        self.Enabled = False
+        self.FollowSpecular = False
+        self.OnlyFirstIteration = True
+
+
 class RuntimeOptions:
     """Subset of IG::RuntimeOptions (src/runtime/RuntimeSettings.h:16-62)."""
 
     def __init__(self):
+        self.Denoiser = DenoiserSettings()
         self.Device = 0          # HIP device ordinal (--gpu-device)
         self.SPI = 0             # 0 = recommended
         self.Seed = 0
@@ -274,8 +305,10 @@ class Device:
         self._check(self._lib.igx_render_iterations(self._h, C.byref(params), int(count)))
 
     def framebuffer(self, count, name=None):
-        """The film, or a named AOV (igx_get_aov: "Color", and with the
-        technique's aov_mis "Direct Weights" / "NEE Weights")."""
+        """The film, or a named AOV (igx_get_aov: "Color", with the
+        technique's aov_mis "Direct Weights" / "NEE Weights", with option
+        "denoise_aovs" "Normals" / "Albedo" / "Depth"), and its iteration
+        count (the denoiser's AOVs count their own passes)."""
         out = np.zeros(count, dtype=np.float32)
         it = C.c_uint64()
         if name is None:
@@ -294,8 +327,19 @@ class Device:
     def pack_tiles(self, params, dst_ptr, count):
         self._check(self._lib.igx_pack_tiles(self._h, C.byref(params), C.c_void_p(dst_ptr), count))
 
-    def clear(self):
-        self._check(self._lib.igx_clear(self._h))
+    def aov_iteration_count(self, name=None):
+        """igx_aov_iteration_count: the count `framebuffer(count, name)` returns, without the copy."""
+        it = C.c_uint64()
+        self._check(self._lib.igx_aov_iteration_count(self._h, name.encode() if name else None, C.byref(it)))
+        return int(it.value)
+
+    def clear(self, name=None):
+        """Everything (igx_clear), or with a name that film and its iteration
+        count only (igx_clear_aov; "Color" is the film)."""
+        if name is None:
+            self._check(self._lib.igx_clear(self._h))
+        else:
+            self._check(self._lib.igx_clear_aov(self._h, name.encode()))
 
     def synchronize(self):
         self._check(self._lib.igx_synchronize(self._h))
@@ -360,6 +404,10 @@ class Runtime:
             self.device.set_option("timing", 1)
         if opts.Capacity:
             self.device.set_option("capacity", opts.Capacity)
+        dn = opts.Denoiser
+        if dn.Enabled:
+            self.device.set_option("denoise_aovs", 1 if dn.OnlyFirstIteration else 2)
+            self.device.set_option("denoise_follow_specular", int(bool(dn.FollowSpecular)))
         self.device.upload(scene)
         self._iteration = 0
         self._frame = 0
@@ -392,12 +440,31 @@ class Runtime:
         """Runtime::getFramebufferForHost(name) (Runtime.cpp:417-435): the
         film ("" / "Color") or a named AOV of the technique."""
         fb, it = self.device.framebuffer(self._fb_count, name or None)
-        self._iters = it
+        if name in ("", "Color"):
+            self._iters = it
         return fb.reshape(self.FilmHeight, self.FilmWidth, 3)
 
-    def clearFramebuffer(self):
-        self.device.clear()
-        self._iters = 0
+    def getFramebufferIterationCount(self, name=""):
+        """The iteration count of the film or of a named AOV (an AOV of the
+        denoiser counts its own passes, Device.cpp:1390-1403)."""
+        return self.device.aov_iteration_count(name or None)
+
+    def aovs(self):
+        """Names of the enabled AOVs (TechniqueInfo::EnabledAOVs)."""
+        names = []
+        if self.scene.desc.technique.aov_mis:
+            names += ["Direct Weights", "NEE Weights"]
+        if self.options.Denoiser.Enabled:
+            names += ["Normals", "Albedo", "Depth"]
+        return names
+
+    def clearFramebuffer(self, name=None):
+        """Runtime::clearFramebuffer() (Runtime.cpp:427-430): everything; with a
+        name, Runtime::clearFramebuffer(name) (:432-435, Device.cpp:1415-1443):
+        the film ("" / "Color") or one AOV, and its iteration count, only."""
+        self.device.clear(None if name is None else (name or "Color"))
+        if name in (None, "", "Color"):
+            self._iters = 0
 
     def reset(self):
         self.clearFramebuffer()

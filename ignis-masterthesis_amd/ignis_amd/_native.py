@@ -152,6 +152,7 @@ EXPORTED_SYMBOLS = [
     "igx_pack_tiles", "igx_clear", "igx_get_stats", "igx_reset_stats", "igx_trace_hits", "igx_trace_occlusion", "igx_synchronize", "igx_wait_ready",
     "igx_render_iterations", "igx_objscene_create", "igx_objscene_free", "igx_objscene_add",
     "igx_objscene_set_property", "igx_scene_from_objects", "igx_set_camera",
+    "igx_clear_aov", "igx_aov_iteration_count", "igx_write_exr_layers",
 ]
 
 _lib = None
@@ -193,6 +194,9 @@ def lib():
     L.igx_set_camera.argtypes = [vp, C.POINTER(Camera)]
     L.igx_write_exr.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_float]
     L.igx_write_exr.restype = C.c_int
+    L.igx_write_exr_layers.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_float)), C.c_int32,
+                                       C.c_int32, C.c_int32, C.POINTER(C.c_float)]
+    L.igx_write_exr_layers.restype = C.c_int
     L.igx_create.argtypes = [C.c_int, C.POINTER(vp)]
     L.igx_destroy.argtypes = [vp]
     L.igx_last_error.argtypes = [vp]
@@ -209,6 +213,8 @@ def lib():
     L.igx_aov_device_ptr.argtypes = [vp, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.igx_pack_tiles.argtypes = [vp, C.POINTER(RenderParams), C.c_void_p, C.c_size_t]
     L.igx_clear.argtypes = [vp]
+    L.igx_clear_aov.argtypes = [vp, C.c_char_p]
+    L.igx_aov_iteration_count.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint64)]
     L.igx_synchronize.argtypes = [vp]
     L.igx_wait_ready.argtypes = [vp]
     L.igx_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -218,7 +224,7 @@ def lib():
     L.igx_trace_occlusion.argtypes = [vp, C.POINTER(C.c_float), C.c_int32, C.c_uint32, C.POINTER(C.c_int32)]
     for name in ["igx_create", "igx_destroy", "igx_set_option", "igx_upload_scene", "igx_render", "igx_render_iterations",
                  "igx_get_framebuffer", "igx_framebuffer_device_ptr", "igx_get_aov", "igx_aov_device_ptr",
-                 "igx_pack_tiles", "igx_clear",
+                 "igx_pack_tiles", "igx_clear", "igx_clear_aov", "igx_aov_iteration_count",
                  "igx_synchronize", "igx_wait_ready", "igx_get_stats", "igx_reset_stats", "igx_trace_hits", "igx_trace_occlusion"]:
         getattr(L, name).restype = C.c_int
     _lib = L

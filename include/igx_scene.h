@@ -318,6 +318,13 @@ igx_scene* igx_scene_from_database(const igx_database_view* db, const igx_shadin
  * `channels` = 3 (RGB) or 4 (RGB + alpha 1).  Replaces Image::save
  * (src/runtime/Image.h:92-101) for the framebuffer output.  0 on success. */
 int igx_write_exr(const char* path, const float* rgb, int32_t width, int32_t height, int32_t channels, float scale);
+/* One file of `n_layers` RGB layers with the channels <names[k]>.R / .G / .B,
+ * layer k = planes_rgb[k] (as `rgb` above) times scales[k]: the reference's
+ * layout of a render with AOVs (frontend/common/IO.cpp:105-129), where the
+ * film is the layer "Default" and every AOV is divided by its own iteration
+ * count.  0 on success; -1 for a bad argument (a layer named twice, too). */
+int igx_write_exr_layers(const char* path, const char* const* names, const float* const* planes_rgb, int32_t n_layers,
+                         int32_t width, int32_t height, const float* scales);
 
 #ifdef __cplusplus
 }
