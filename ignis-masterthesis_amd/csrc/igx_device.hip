@@ -31,6 +31,7 @@
 #include "../host/light_select.h"
 #include "../host/lds_plan.h"
 #include "../host/aov_plan.h"
+#include "../host/film_tools.h"
 
 #include <hip/hip_runtime.h>
 
@@ -56,7 +57,8 @@ using namespace igxd;
 //   0 = host driver, C-ABI and the small kernels; 1 = k_extend variants;
 //   2 = k_finish variants; 3 = k_trace / k_trace_refill / k_shade / k_shadow /
 //   k_shadow_refill variants; 4 = the wide (BLOCK_WIDE-thread) k_extend variants;
-//   5 = the k_infobuffer variants.  Types and device functions are shared; each
+//   5 = the k_infobuffer variants; 6 = the film post-processing kernels
+//   (igx_post.h).  Types and device functions are shared; each
 //   part instantiates only its own launch helpers (explicit instantiation),
 //   the others see them as extern templates.
 #ifndef IGX_PART
@@ -2070,6 +2072,11 @@ struct igx_device {
     // option "timing": the event pairs around the info-buffer passes queued
     // since the last drain (folded into ms_generate there)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> info_timed;
+    // film post-processing scratch (igx_tonemap / igx_imageinfo, igx_post.h):
+    // the luminance plane, the per-block slab, the result + histograms and the
+    // packed image; grown on demand, rewritten by every call
+    void* post_buf[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t post_cap[4] = {0, 0, 0, 0};
     // stats
     igx_stats stats{};
     // asynchronous rendering (option "async_render"): the worker thread and
@@ -2537,6 +2544,40 @@ void launch_infobuffer(igx_device* dev, int grid, hipStream_t strm, const FrameA
 }
 #endif
 
+// Film post-processing (igx_post.h, part 6): tone curve arguments, the
+// per-block partial results of the imageinfo passes (pass 1: one entry per
+// POST_CHUNK pixels; pass 2: one per block of 3x3 windows) and the result
+// k_info_final leaves in device memory (16 words, the histograms behind it)
+struct PostTonemap {
+    float scale;
+    int method, use_gamma;
+    float exposure_factor, exposure_offset;
+};
+struct PostSlab {
+    float *mn, *mx, *sum;
+    int *n_inf, *n_nan, *n_neg;
+    float *smin, *smax, *med;
+};
+struct PostResult {
+    float min, max, avg, soft_min, soft_max, median;
+    int inf_count, nan_count, neg_count;
+    float start, factor; // of the histograms
+    int pad[5];
+};
+// histograms of more than this many bytes (4 * bins ints) count in global memory
+[[maybe_unused]] constexpr size_t POST_HIST_LDS_MAX = 32 * 1024;
+// queue k_tonemap on dev->stream: `pixels` RGB pixels of `film` to packed ARGB in `out` (both device memory)
+void launch_tonemap(igx_device* dev, const float* film, size_t pixels, const PostTonemap& a, uint32_t* out);
+// slab entries of the two imageinfo passes (pass 2: 0 unless w > 10 && h > 10)
+int post_lum_blocks(size_t n);
+int post_soft_blocks(int w, int h);
+// queue the imageinfo passes on dev->stream; hist (4 * bins ints, zeroed on the stream before) may be nullptr
+void launch_imageinfo(igx_device* dev, const float* film, int w, int h, float scale, bool stats, int bins, float* plane, const PostSlab& s,
+                      PostResult* res, int* hist);
+#if IGX_PART == 6
+#include "igx_post.h"
+#endif
+
 // Launch helpers: defined (explicitly instantiated) in their part, extern elsewhere.
 #define IGX_EXTEND_HELPERS(X, S)                                                                                     \
     X void launch_extend<S>(igx_device*, Slot&, int, const FrameArgs&, const PathBuf&, const PathBuf&,               \
@@ -2852,6 +2893,8 @@ extern "C" igx_status igx_destroy(igx_device* dev) {
     if (dev->dstats) (void)hipFree(dev->dstats);
     if (dev->tail_counts) (void)hipFree(dev->tail_counts);
     if (dev->ray_list) (void)hipFree(dev->ray_list);
+    for (void* b : dev->post_buf)
+        if (b) (void)hipFree(b);
     if (dev->stream) (void)hipStreamDestroy(dev->stream);
     if (dev->stream2) (void)hipStreamDestroy(dev->stream2);
     if (dev->tail_stream) (void)hipStreamDestroy(dev->tail_stream);
@@ -4754,6 +4797,127 @@ extern "C" igx_status igx_framebuffer_device_ptr(igx_device* dev, float** ptr, s
     *ptr = dev->fb;
     if (count) *count = dev->fb_count;
     return IGX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Film post-processing (Device::tonemap / Device::imageinfo, Device.cpp:1662-1759)
+// ---------------------------------------------------------------------------
+enum { POST_PLANE = 0, POST_SLAB = 1, POST_RESULT = 2, POST_PIXELS = 3 };
+// the handle's scratch buffer `which`, at least `bytes` large (the stream is idle: every post call ends in a wait)
+static igx_status post_reserve(igx_device* dev, int which, size_t bytes) {
+    if (dev->post_cap[which] >= bytes) return IGX_OK;
+    if (dev->post_buf[which]) HIPCHK(hipFree(dev->post_buf[which]));
+    dev->post_buf[which] = nullptr;
+    dev->post_cap[which] = 0;
+    HIPCHK(hipMalloc(&dev->post_buf[which], bytes));
+    dev->post_cap[which] = bytes;
+    return IGX_OK;
+}
+
+// the queue is drained; film: pixels RGB floats in device memory
+static igx_status tonemap_run(igx_device* dev, const float* film, size_t pixels, float scale, const igx_tonemap_settings* ts,
+                              uint32_t* out, bool out_on_device) {
+    uint32_t* dst = out;
+    if (!out_on_device) {
+        igx_status st = post_reserve(dev, POST_PIXELS, pixels * sizeof(uint32_t));
+        if (st != IGX_OK) return st;
+        dst = (uint32_t*)dev->post_buf[POST_PIXELS];
+    }
+    const PostTonemap a{scale, ts->method, ts->use_gamma ? 1 : 0, ts->exposure_factor, ts->exposure_offset};
+    launch_tonemap(dev, film, pixels, a, dst);
+    HIPCHK(hipGetLastError());
+    if (!out_on_device) HIPCHK(hipMemcpyAsync(out, dst, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, dev->stream));
+    HIPCHK(hipStreamSynchronize(dev->stream));
+    return IGX_OK;
+}
+
+static igx_status imageinfo_run(igx_device* dev, const float* film, int w, int h, float scale, const igx_imageinfo_settings* is,
+                                igx_imageinfo_output* out) {
+    const size_t n = (size_t)w * h;
+    int32_t* host_hist[4] = {is->histogram_r, is->histogram_g, is->histogram_b, is->histogram_l};
+    const bool want_hist = is->acquire_histogram && is->bins > 0 && (host_hist[0] || host_hist[1] || host_hist[2] || host_hist[3]);
+    const size_t bins = want_hist ? (size_t)is->bins : 0;
+    const size_t b1 = (size_t)post_lum_blocks(n), b2 = (size_t)post_soft_blocks(w, h);
+    const size_t result_words = sizeof(PostResult) / sizeof(int) + 4 * bins;
+    igx_status st;
+    if ((st = post_reserve(dev, POST_PLANE, n * sizeof(float))) || (st = post_reserve(dev, POST_SLAB, (6 * b1 + 3 * b2 + 1) * sizeof(float))) ||
+        (st = post_reserve(dev, POST_RESULT, result_words * sizeof(int))))
+        return st;
+    float* sf = (float*)dev->post_buf[POST_SLAB];
+    PostSlab s;
+    s.mn = sf, s.mx = sf + b1, s.sum = sf + 2 * b1;
+    s.n_inf = (int*)(sf + 3 * b1), s.n_nan = (int*)(sf + 4 * b1), s.n_neg = (int*)(sf + 5 * b1);
+    s.smin = sf + 6 * b1, s.smax = sf + 6 * b1 + b2, s.med = sf + 6 * b1 + 2 * b2;
+    PostResult* res = (PostResult*)dev->post_buf[POST_RESULT];
+    int* hist = want_hist ? (int*)(res + 1) : nullptr;
+    HIPCHK(hipMemsetAsync(res, 0, result_words * sizeof(int), dev->stream));
+    launch_imageinfo(dev, film, w, h, scale, is->acquire_error_stats != 0, (int)is->bins, (float*)dev->post_buf[POST_PLANE], s, res, hist);
+    HIPCHK(hipGetLastError());
+    std::vector<int> back(result_words);
+    HIPCHK(hipMemcpyAsync(back.data(), res, result_words * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+    HIPCHK(hipStreamSynchronize(dev->stream));
+    PostResult r;
+    std::memcpy(&r, back.data(), sizeof(r));
+    *out = igx_imageinfo_output{r.min, r.max, r.avg, r.soft_min, r.soft_max, r.median, r.inf_count, r.nan_count, r.neg_count};
+    for (int c = 0; c < 4 && want_hist; ++c)
+        if (host_hist[c]) std::memcpy(host_hist[c], back.data() + sizeof(PostResult) / sizeof(int) + c * bins, bins * sizeof(int));
+    return IGX_OK;
+}
+
+// resolves `name` to the handle's film (nullptr before the first render with
+// it) and the scale of one iteration (Device.cpp:1668,1675), after a drain
+static igx_status post_named_film(igx_device* dev, const char* name, float scale, const float** film, float* film_scale) {
+    const int k = aov_index(dev, name);
+    if (k == AOV_UNKNOWN) return fail(dev, IGX_ERR_INVALID_ARGUMENT, std::string("unknown aov '") + (name ? name : "") + "'");
+    HIPCHK(hipSetDevice(dev->hip_device));
+    igx_status st = drain(dev);
+    if (st != IGX_OK) return st;
+    *film = k == AOV_COLOR ? dev->fb : aov_film(dev, k);
+    const uint64_t iters = k == AOV_COLOR ? dev->iteration_count : aov_count(dev, k);
+    *film_scale = scale * (iters > 0 ? 1.0f / (float)iters : 0.0f);
+    return IGX_OK;
+}
+
+extern "C" igx_status igx_tonemap(igx_device* dev, const char* aov, const igx_tonemap_settings* ts, uint32_t* out_host, size_t pixel_count) {
+    if (!dev || !ts || !out_host || pixel_count == 0) return IGX_ERR_INVALID_ARGUMENT;
+    const float* film = nullptr;
+    float scale = 0;
+    igx_status st = post_named_film(dev, aov, ts->scale, &film, &scale);
+    if (st != IGX_OK || !film) return st;
+    if (pixel_count * 3 != dev->fb_count)
+        return fail(dev, IGX_ERR_INVALID_ARGUMENT, "tonemap size mismatch: expected " + std::to_string(dev->fb_count / 3) + " pixels");
+    return tonemap_run(dev, film, pixel_count, scale, ts, out_host, false);
+}
+
+extern "C" igx_status igx_imageinfo(igx_device* dev, const char* aov, const igx_imageinfo_settings* is, igx_imageinfo_output* out) {
+    if (!dev || !is || !out || is->bins < 0) return IGX_ERR_INVALID_ARGUMENT;
+    const float* film = nullptr;
+    float scale = 0;
+    igx_status st = post_named_film(dev, aov, is->scale, &film, &scale);
+    if (st != IGX_OK) return st;
+    if (!film) {
+        *out = igx_imageinfo_output{0, 0, 0, 0, 0, 0, 0, 0, 0};
+        return IGX_OK;
+    }
+    return imageinfo_run(dev, film, dev->fb_w, dev->fb_h, scale, is, out);
+}
+
+extern "C" igx_status igx_tonemap_film(igx_device* dev, const float* film_dev, int32_t width, int32_t height, const igx_tonemap_settings* ts,
+                                       uint32_t* out_pixels, int32_t out_on_device) {
+    if (!dev || !film_dev || !ts || !out_pixels || width <= 0 || height <= 0) return IGX_ERR_INVALID_ARGUMENT;
+    HIPCHK(hipSetDevice(dev->hip_device));
+    igx_status st = drain(dev);
+    if (st != IGX_OK) return st;
+    return tonemap_run(dev, film_dev, (size_t)width * height, ts->scale, ts, out_pixels, out_on_device != 0);
+}
+
+extern "C" igx_status igx_imageinfo_film(igx_device* dev, const float* film_dev, int32_t width, int32_t height,
+                                         const igx_imageinfo_settings* is, igx_imageinfo_output* out) {
+    if (!dev || !film_dev || !is || !out || is->bins < 0 || width <= 0 || height <= 0) return IGX_ERR_INVALID_ARGUMENT;
+    HIPCHK(hipSetDevice(dev->hip_device));
+    igx_status st = drain(dev);
+    if (st != IGX_OK) return st;
+    return imageinfo_run(dev, film_dev, width, height, is->scale, is, out);
 }
 
 extern "C" igx_status igx_pack_tiles(igx_device* dev, const igx_render_params* p, float* dst, size_t count) {

@@ -26,9 +26,11 @@
 //     file;
 //   * the framebuffer, statistics, resize and release calls map one to one.
 // tonemap / evaluateGlare / imageinfo / bake (Device.h:66-69) are outside the
-// hot path ("stub or CPU fallback"): tonemap and imageinfo run
-// on the host over getFramebufferForHost (restating entrypoints/tonemap.art and
-// entrypoints/imageinfo.art with core/color.art); evaluateGlare and bake have
+// traced path: tonemap and imageinfo run on the device over the film where it
+// lies (igx_tonemap / igx_imageinfo: entrypoints/tonemap.art and
+// entrypoints/imageinfo.art with core/color.art as HIP kernels; only the packed
+// image or the statistics are copied back; film_tools.h keeps the same
+// arithmetic as host loops); evaluateGlare and bake have
 // no igx counterpart (the glare shader needs the camera's solid-angle model,
 // bake a compiled shading-tree shader) and log and return an empty result.
 // Errors from the C-ABI become std::runtime_error, which a Runtime turns into
@@ -374,13 +376,13 @@ public:
         return &mStats;
     }
 
-    // entrypoints/tonemap.art on the host over the AOV's host copy (film_tools.h)
+    // entrypoints/tonemap.art on the device over the AOV's film (igx_tonemap);
+    // an unknown AOV or no film yet leaves out_pixels untouched
     void tonemap(uint32_t* out_pixels, const TonemapSettings& ts) {
-        const AOVAccessor acc = getFramebufferForHost(ts.AOV ? ts.AOV : "");
-        if (!acc.Data || !out_pixels) return;
-        const float inv_iter = acc.IterationCount > 0 ? 1.0f / (float)acc.IterationCount : 0.0f;
-        igx::tonemap_film(acc.Data, mWidth * mHeight, ts.Scale * inv_iter, (int)ts.Method, ts.UseGamma, ts.ExposureFactor,
-                          ts.ExposureOffset, out_pixels);
+        const std::string name = ts.AOV ? ts.AOV : "";
+        if (!knownAOV(name) || !out_pixels || mWidth * mHeight == 0) return;
+        const igx_tonemap_settings s{(int32_t)ts.Method, ts.UseGamma ? 1 : 0, ts.Scale, ts.ExposureFactor, ts.ExposureOffset};
+        check(igx_tonemap(mDev, name.c_str(), &s, out_pixels, mWidth * mHeight));
     }
     // The glare shader (Device.cpp:1689-1723) evaluates the daylight glare
     // probability over the camera's solid-angle model; igx has none: logged, empty
@@ -388,13 +390,15 @@ public:
         std::fprintf(stderr, "igx: evaluateGlare is not provided by the igx device (outside the traced path)\n");
         return GlareOutput{0, 0, 0, 0, 0};
     }
-    // entrypoints/imageinfo.art on the host over the AOV's host copy (film_tools.h)
+    // entrypoints/imageinfo.art on the device over the AOV's film
+    // (igx_imageinfo); an unknown AOV or no film yet gives the all-zero result
     ImageInfoOutput imageinfo(const ImageInfoSettings& is) {
-        const AOVAccessor acc = getFramebufferForHost(is.AOV ? is.AOV : "");
-        if (!acc.Data) return ImageInfoOutput{0, 0, 0, 0, 0, 0, 0, 0, 0};
-        const float inv_iter = acc.IterationCount > 0 ? 1.0f / (float)acc.IterationCount : 0.0f;
-        const igx::FilmInfo f = igx::imageinfo_film(acc.Data, mWidth, mHeight, is.Scale * inv_iter, is.Bins, is.HistogramR, is.HistogramG,
-                                                    is.HistogramB, is.HistogramL, is.AcquireErrorStats, is.AcquireHistogram);
+        const std::string name = is.AOV ? is.AOV : "";
+        if (!knownAOV(name)) return ImageInfoOutput{0, 0, 0, 0, 0, 0, 0, 0, 0};
+        const igx_imageinfo_settings s{is.Scale,      (int32_t)is.Bins,           is.HistogramR, is.HistogramG, is.HistogramB,
+                                       is.HistogramL, is.AcquireErrorStats ? 1 : 0, is.AcquireHistogram ? 1 : 0};
+        igx_imageinfo_output f{};
+        check(igx_imageinfo(mDev, name.c_str(), &s, &f));
         return ImageInfoOutput{f.min, f.max, f.avg, f.soft_min, f.soft_max, f.median, f.inf_count, f.nan_count, f.neg_count};
     }
     // Device::bake (Device.cpp:1761-1774) runs a shading-tree shader compiled

@@ -15,12 +15,21 @@
 #include <cstdint>
 #include <vector>
 
+// The pure colour helpers are also the device functions of the film
+// post-processing kernels (csrc/igx_post.h): one statement of the arithmetic
+// for the host loops below and for the GPU.
+#ifdef __HIPCC__
+#define IGX_FILM_HD __host__ __device__
+#else
+#define IGX_FILM_HD
+#endif
+
 namespace igx {
 
 struct FilmColor { float r, g, b; };
 
 // core/color.art:84-100: sRGB -> CIE xyY (Y is the luminance) and back
-inline FilmColor srgb_to_xyY(FilmColor c) {
+IGX_FILM_HD inline FilmColor srgb_to_xyY(FilmColor c) {
     const float X = 0.4124564f * c.r + 0.3575761f * c.g + 0.1804375f * c.b;
     const float Y = 0.2126729f * c.r + 0.7151522f * c.g + 0.0721750f * c.b;
     const float Z = 0.0193339f * c.r + 0.1191920f * c.g + 0.9503041f * c.b;
@@ -28,16 +37,16 @@ inline FilmColor srgb_to_xyY(FilmColor c) {
     if (n <= 1.1920929e-7f) return FilmColor{0, 0, 0};
     return FilmColor{X / n, Y / n, Y};
 }
-inline FilmColor xyY_to_srgb(FilmColor c) {
+IGX_FILM_HD inline FilmColor xyY_to_srgb(FilmColor c) {
     if (c.g <= 1.1920929e-7f) return FilmColor{0, 0, 0};
     const float X = c.r * c.b / c.g, Y = c.b, Z = (1 - c.r - c.g) * c.b / c.g;
     return FilmColor{3.2404542f * X - 1.5371385f * Y - 0.4985314f * Z, -0.9692660f * X + 1.8760108f * Y + 0.0415560f * Z,
                      0.0556434f * X - 0.2040259f * Y + 1.0572252f * Z};
 }
-inline float film_safe_div(float a, float b) { return b == 0 ? 0.0f : a / b; }
+IGX_FILM_HD inline float film_safe_div(float a, float b) { return b == 0 ? 0.0f : a / b; }
 // mod tonemapping (core/color.art:101-134): 0 none, 1 Reinhard, 2 modified
 // Reinhard (white point 4), 3 ACES (Narkowicz 2015), else Uncharted 2
-inline float tonemap_curve(int method, float L) {
+IGX_FILM_HD inline float tonemap_curve(int method, float L) {
     switch (method) {
     case 0: return L;
     case 1: return film_safe_div(L, 1.0f + L);
@@ -51,9 +60,9 @@ inline float tonemap_curve(int method, float L) {
     }
     }
 }
-inline float srgb_gamma(float x) { return x <= 0.0031308f ? 12.92f * x : 1.055f * std::pow(x, 0.416666667f) - 0.055f; }
-inline uint32_t packed_color(uint32_t r, uint32_t g, uint32_t b, uint32_t a) { return (a << 24) | (r << 16) | (g << 8) | b; }
-inline uint32_t color_byte(float v) { return (uint32_t)(uint8_t)(std::min(std::max(v, 0.0f), 1.0f) * 255); }
+IGX_FILM_HD inline float srgb_gamma(float x) { return x <= 0.0031308f ? 12.92f * x : 1.055f * std::pow(x, 0.416666667f) - 0.055f; }
+IGX_FILM_HD inline uint32_t packed_color(uint32_t r, uint32_t g, uint32_t b, uint32_t a) { return (a << 24) | (r << 16) | (g << 8) | b; }
+IGX_FILM_HD inline uint32_t color_byte(float v) { return (uint32_t)(uint8_t)(std::min(std::max(v, 0.0f), 1.0f) * 255); }
 
 // ig_tonemap_pipeline: each pixel scaled by `scale` (the caller's Scale /
 // IterationCount), to xyY; NaN luminance cyan, inf pink, a negative

@@ -17,7 +17,11 @@
 // one with --denoiser-aov-every-iteration; --denoiser-follow-specular as the
 // reference's flag (ProgramOptions.cpp:211-213); -o then writes one EXR with
 // the layers Default / Normals / Albedo / Depth, each over its own iteration
-// count (frontend/common/IO.cpp:72-129).  Options of the reference's other targets and of its
+// count (frontend/common/IO.cpp:72-129).  --imageinfo [BINS] prints one line
+// `imageinfo {json}` with the film's luminance statistics (and with BINS the
+// four histograms), --ppm FILE [--tonemap N] [--gamma] writes the tonemapped
+// film as a binary PPM; both run on the device (Device::imageinfo /
+// Device::tonemap).  Options of the reference's other targets and of its
 // shader compiler are refused with a message.
 #include "Device.h"
 #include "igx_scene.h"
@@ -35,6 +39,7 @@ static void usage() {
                  "usage: igcli SCENE.json [--spp N | --time SECONDS] [--spi N] [--seed N] [--gpu] [--gpu-device N]\n"
                  "             [--width W --height H] [--eye X Y Z] [--dir X Y Z] [--up X Y Z] [--stats]\n"
                  "             [--denoise-aovs [--denoiser-aov-every-iteration] [--denoiser-follow-specular]]\n"
+                 "             [--imageinfo [BINS]] [--ppm out.ppm [--tonemap 0..4] [--gamma]]\n"
                  "             [-o out.exr|out.pfm]\n");
 }
 
@@ -43,6 +48,10 @@ int main(int argc, char** argv) {
     int spp = 0, spi = 8, seed = 0, device = 0, width = 0, height = 0;
     double render_time = 0; // --time: seconds of rendering instead of a sample count
     bool stats = false;
+    int info_bins = -1; // --imageinfo: -1 off, 0 statistics only, n > 0 with histograms of n bins
+    std::string ppm_path;
+    int tonemap_method = 0;
+    bool tonemap_gamma = false;
     IG::Device::DenoiserSettings denoiser;
     IG::ParameterSet params; // the camera orientation overrides (__camera_eye / _dir / _up)
     for (int i = 1; i < argc; ++i) {
@@ -77,6 +86,14 @@ int main(int argc, char** argv) {
         else if (a == "--denoiser-aov-first-iteration") denoiser.OnlyFirstIteration = true;
         else if (a == "--denoiser-follow-specular") denoiser.FollowSpecular = true;
         else if (a == "--denoiser-skip-specular") denoiser.FollowSpecular = false;
+        else if (a == "--imageinfo") {
+            info_bins = 0;
+            if (i + 1 < argc && argv[i + 1][0] && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1]))
+                info_bins = std::atoi(argv[++i]);
+        }
+        else if (a == "--ppm") ppm_path = next();
+        else if (a == "--tonemap") tonemap_method = std::atoi(next());
+        else if (a == "--gamma") tonemap_gamma = true;
         else if (a == "-o" || a == "--output") out_path = next();
         else if (a == "--gpu" || a == "--no-progress" || a == "--no-color" || a == "-q" || a == "--quiet") {}
         else if (a == "--cpu" || a == "--cpu-arch" || a == "--cpu-threads" || a == "--cpu-vectorwidth") {
@@ -145,6 +162,40 @@ int main(int argc, char** argv) {
             const size_t all_ms = (size_t)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all).count());
             std::printf("%s  Iterations: %zu\n  SPP: %zu\n  SPI: %d\n", dev.getStatistics()->dump(all_ms, rates.size()).c_str(),
                         rates.size(), rates.size() * (size_t)spi, spi);
+        }
+        if (info_bins >= 0) {
+            std::vector<int> hist[4];
+            for (auto& h : hist) h.assign((size_t)std::max(info_bins, 1), 0);
+            const IG::ImageInfoSettings is{"", 1.0f, (size_t)info_bins, hist[0].data(), hist[1].data(), hist[2].data(), hist[3].data(),
+                                           true, info_bins > 0};
+            const IG::ImageInfoOutput io = dev.imageinfo(is);
+            // %.9g round-trips a float
+            std::printf("imageinfo {\"min\": %.9g, \"max\": %.9g, \"avg\": %.9g, \"soft_min\": %.9g, \"soft_max\": %.9g, "
+                        "\"median\": %.9g, \"inf_count\": %d, \"nan_count\": %d, \"neg_count\": %d",
+                        io.Min, io.Max, io.Average, io.SoftMin, io.SoftMax, io.Median, io.InfCount, io.NaNCount, io.NegCount);
+            const char* names[4] = {"histogram_r", "histogram_g", "histogram_b", "histogram_l"};
+            for (int c = 0; c < 4 && info_bins > 0; ++c) {
+                std::printf(", \"%s\": [", names[c]);
+                for (int k = 0; k < info_bins; ++k) std::printf(k ? ", %d" : "%d", hist[c][k]);
+                std::printf("]");
+            }
+            std::printf("}\n");
+        }
+        if (!ppm_path.empty()) {
+            std::vector<uint32_t> px((size_t)W * H, 0xff000000u);
+            dev.tonemap(px.data(), IG::TonemapSettings{"", (size_t)tonemap_method, tonemap_gamma, 1.0f, 1.0f, 0.0f});
+            FILE* f = std::fopen(ppm_path.c_str(), "wb");
+            if (!f) { std::fprintf(stderr, "cannot write %s\n", ppm_path.c_str()); return 1; }
+            std::fprintf(f, "P6\n%d %d\n255\n", W, H);
+            std::vector<unsigned char> row(3 * (size_t)W);
+            for (int y = 0; y < H; ++y) {
+                for (int x = 0; x < W; ++x) {
+                    const uint32_t p = px[(size_t)y * W + x];
+                    row[3 * x] = (unsigned char)(p >> 16), row[3 * x + 1] = (unsigned char)(p >> 8), row[3 * x + 2] = (unsigned char)p;
+                }
+                std::fwrite(row.data(), 1, row.size(), f);
+            }
+            std::fclose(f);
         }
         if (!out_path.empty()) {
             IG::Device::AOVAccessor acc = dev.getFramebufferForHost("");

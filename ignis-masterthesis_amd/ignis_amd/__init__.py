@@ -21,7 +21,8 @@ import os
 import numpy as np
 
 from . import _native
-from ._native import EXPORTED_SYMBOLS, LIB_PATH, RenderParams, Stats, lib
+from ._native import (EXPORTED_SYMBOLS, LIB_PATH, ImageInfoOutput, ImageInfoSettings, RenderParams, Stats,
+                      TonemapSettings, lib)
 
 __all__ = ["RuntimeOptions", "DenoiserSettings", "Scene", "Runtime", "loadFromFile", "loadFromString", "version",
            "EXPORTED_SYMBOLS", "LIB_PATH", "IgxError"]
@@ -280,6 +281,7 @@ class Device:
         if st != 0 or not h:
             raise IgxError(f"igx_create({hip_device}) failed with status {st}")
         self._h = h
+        self._film = None  # (width, height) of the last render: the shape of tonemap()
 
     def _check(self, st):
         if st != 0:
@@ -291,8 +293,12 @@ class Device:
     def upload(self, scene):
         self._check(self._lib.igx_upload_scene(self._h, scene.desc_ptr))
 
+    def _rendered(self, params):
+        self._film = (params.num_rays, 1) if params.num_rays > 0 else (params.width, params.height)
+
     def render(self, params):
         self._check(self._lib.igx_render(self._h, C.byref(params)))
+        self._rendered(params)
 
     def set_camera(self, camera):
         """Replace the uploaded scene's camera (an N.Camera; igx_set_camera, as
@@ -303,6 +309,7 @@ class Device:
     def render_iterations(self, params, count):
         """`count` consecutive iterations from params.iteration (igx_render_iterations)."""
         self._check(self._lib.igx_render_iterations(self._h, C.byref(params), int(count)))
+        self._rendered(params)
 
     def framebuffer(self, count, name=None):
         """The film, or a named AOV (igx_get_aov: "Color", with the
@@ -340,6 +347,65 @@ class Device:
             self._check(self._lib.igx_clear(self._h))
         else:
             self._check(self._lib.igx_clear_aov(self._h, name.encode()))
+
+    # ---- film post-processing on the device (igx_tonemap / igx_imageinfo) ----
+    @staticmethod
+    def _tonemap_settings(method, use_gamma, scale, exposure_factor, exposure_offset):
+        return TonemapSettings(int(method), int(bool(use_gamma)), float(scale), float(exposure_factor), float(exposure_offset))
+
+    def tonemap(self, name=None, method=0, use_gamma=False, scale=1.0, exposure_factor=1.0, exposure_offset=0.0):
+        """Device::tonemap of the film or a named AOV, scaled by scale / its
+        iteration count: an (h, w) uint32 array of (a << 24) | (r << 16) |
+        (g << 8) | b words (method: 0 none, 1 Reinhard, 2 modified Reinhard,
+        3 ACES, else Uncharted 2).  None before the first render."""
+        if self._film is None:
+            return None
+        w, h = self._film
+        out = np.zeros((h, w), dtype=np.uint32)
+        ts = self._tonemap_settings(method, use_gamma, scale, exposure_factor, exposure_offset)
+        self._check(self._lib.igx_tonemap(self._h, name.encode() if name else None, C.byref(ts),
+                                          out.ctypes.data_as(C.POINTER(C.c_uint32)), w * h))
+        return out
+
+    def tonemap_film(self, ptr, w, h, method=0, use_gamma=False, scale=1.0, exposure_factor=1.0, exposure_offset=0.0,
+                     out_ptr=None):
+        """igx_tonemap_film over w * h * 3 floats at the device pointer `ptr`
+        (e.g. tensor.data_ptr()), `scale` as given.  Returns the (h, w) uint32
+        image, or with `out_ptr` (device memory for w * h words) writes there
+        and returns None."""
+        ts = self._tonemap_settings(method, use_gamma, scale, exposure_factor, exposure_offset)
+        if out_ptr is not None:
+            self._check(self._lib.igx_tonemap_film(self._h, C.c_void_p(ptr), int(w), int(h), C.byref(ts), C.c_void_p(out_ptr), 1))
+            return None
+        out = np.zeros((h, w), dtype=np.uint32)
+        self._check(self._lib.igx_tonemap_film(self._h, C.c_void_p(ptr), int(w), int(h), C.byref(ts), C.c_void_p(out.ctypes.data), 0))
+        return out
+
+    def _imageinfo(self, call, scale, bins, error_stats):
+        bins = int(bins)
+        hist = np.zeros((4, max(bins, 1)), dtype=np.int32)
+        ptrs = [hist[c].ctypes.data_as(C.POINTER(C.c_int32)) if bins > 0 else None for c in range(4)]
+        st = ImageInfoSettings(float(scale), bins, *ptrs, int(bool(error_stats)), int(bins > 0))
+        out = ImageInfoOutput()
+        self._check(call(C.byref(st), C.byref(out)))
+        res = {k: getattr(out, k) for k, _ in ImageInfoOutput._fields_}
+        if bins > 0:
+            for c, k in enumerate("rgbl"):
+                res["histogram_" + k] = hist[c].copy()
+        return res
+
+    def imageinfo(self, name=None, scale=1.0, bins=0, error_stats=True):
+        """Device::imageinfo of the film or a named AOV (scaled by scale / its
+        iteration count): a dict of min, max, avg, soft_min, soft_max, median,
+        inf_count, nan_count, neg_count and, with bins > 0, histogram_r / _g /
+        _b / _l (int32 arrays of `bins`)."""
+        aov = name.encode() if name else None
+        return self._imageinfo(lambda st, out: self._lib.igx_imageinfo(self._h, aov, st, out), scale, bins, error_stats)
+
+    def imageinfo_film(self, ptr, w, h, scale=1.0, bins=0, error_stats=True):
+        """igx_imageinfo_film over w * h * 3 floats at the device pointer `ptr`, `scale` as given."""
+        return self._imageinfo(lambda st, out: self._lib.igx_imageinfo_film(self._h, C.c_void_p(ptr), int(w), int(h), st, out),
+                               scale, bins, error_stats)
 
     def synchronize(self):
         self._check(self._lib.igx_synchronize(self._h))
@@ -481,6 +547,14 @@ class Runtime:
         fb, it = self.device.framebuffer(rays.shape[0] * 3)
         self.device.clear()
         return fb.reshape(-1, 3) / max(it, 1)
+
+    def tonemap(self, name="", **settings):
+        """Runtime::tonemap (Runtime.cpp:637): Device.tonemap of the runtime's film or AOV."""
+        return self.device.tonemap(name or None, **settings)
+
+    def imageinfo(self, name="", **settings):
+        """Runtime::imageinfo (Runtime.cpp:663): Device.imageinfo of the runtime's film or AOV."""
+        return self.device.imageinfo(name or None, **settings)
 
     def getStatistics(self):
         return self.device.stats()

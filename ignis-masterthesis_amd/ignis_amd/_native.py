@@ -143,6 +143,24 @@ class Stats(C.Structure):
                 for name, _ in self._fields_}
 
 
+class TonemapSettings(C.Structure):
+    _fields_ = [("method", C.c_int32), ("use_gamma", C.c_int32), ("scale", C.c_float), ("exposure_factor", C.c_float),
+                ("exposure_offset", C.c_float)]
+
+
+class ImageInfoSettings(C.Structure):
+    _fields_ = [("scale", C.c_float), ("bins", C.c_int32),
+                ("histogram_r", C.POINTER(C.c_int32)), ("histogram_g", C.POINTER(C.c_int32)),
+                ("histogram_b", C.POINTER(C.c_int32)), ("histogram_l", C.POINTER(C.c_int32)),
+                ("acquire_error_stats", C.c_int32), ("acquire_histogram", C.c_int32)]
+
+
+class ImageInfoOutput(C.Structure):
+    _fields_ = [("min", C.c_float), ("max", C.c_float), ("avg", C.c_float), ("soft_min", C.c_float),
+                ("soft_max", C.c_float), ("median", C.c_float), ("inf_count", C.c_int32), ("nan_count", C.c_int32),
+                ("neg_count", C.c_int32)]
+
+
 # every symbol include/igx.h and include/igx_scene.h declare
 EXPORTED_SYMBOLS = [
     "igx_scene_load_file", "igx_scene_load_string", "igx_scene_get_desc", "igx_scene_free", "igx_write_exr",
@@ -153,6 +171,7 @@ EXPORTED_SYMBOLS = [
     "igx_render_iterations", "igx_objscene_create", "igx_objscene_free", "igx_objscene_add",
     "igx_objscene_set_property", "igx_scene_from_objects", "igx_set_camera",
     "igx_clear_aov", "igx_aov_iteration_count", "igx_write_exr_layers",
+    "igx_tonemap", "igx_imageinfo", "igx_tonemap_film", "igx_imageinfo_film",
 ]
 
 _lib = None
@@ -222,6 +241,12 @@ def lib():
     L.igx_trace_hits.argtypes = [vp, C.POINTER(C.c_float), C.c_int32, C.c_uint32, C.POINTER(C.c_int32),
                                  C.POINTER(C.c_float)]
     L.igx_trace_occlusion.argtypes = [vp, C.POINTER(C.c_float), C.c_int32, C.c_uint32, C.POINTER(C.c_int32)]
+    L.igx_tonemap.argtypes = [vp, C.c_char_p, C.POINTER(TonemapSettings), C.POINTER(C.c_uint32), C.c_size_t]
+    L.igx_imageinfo.argtypes = [vp, C.c_char_p, C.POINTER(ImageInfoSettings), C.POINTER(ImageInfoOutput)]
+    L.igx_tonemap_film.argtypes = [vp, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(TonemapSettings), C.c_void_p, C.c_int32]
+    L.igx_imageinfo_film.argtypes = [vp, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ImageInfoSettings), C.POINTER(ImageInfoOutput)]
+    for name in ["igx_tonemap", "igx_imageinfo", "igx_tonemap_film", "igx_imageinfo_film"]:
+        getattr(L, name).restype = C.c_int
     for name in ["igx_create", "igx_destroy", "igx_set_option", "igx_upload_scene", "igx_render", "igx_render_iterations",
                  "igx_get_framebuffer", "igx_framebuffer_device_ptr", "igx_get_aov", "igx_aov_device_ptr",
                  "igx_pack_tiles", "igx_clear", "igx_clear_aov", "igx_aov_iteration_count",
