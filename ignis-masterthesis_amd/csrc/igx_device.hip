@@ -151,9 +151,12 @@ struct PathBuf {
 struct ShadowBuf {
     float4* s0; // org.xyz, slot
     float4* s1; // dir.xyz, tmax
-    float4* s2; // colour.rgb, -
+    float4* s2; // colour.rgb, -: added to the slot if the ray is unoccluded; for a class-A record
+                // under `optimistic` the slot's value before k_extend added the colour (undo.rgb, -),
+                // stored back to the slot if the ray is occluded
     int shard_cap;
     float4* aov_nee; // "NEE Weights" per path slot (technique aov_mis), nullptr: off
+    int optimistic;  // FrameArgs::shadow_optimistic of the launch that wrote the records
 };
 struct HitBuf {
     float4* h;  // t, u, v, entity (int bits; -1 = miss)
@@ -176,6 +179,8 @@ struct FrameArgs {
     int classify;        // surviving paths' stream class (see wave_append_paths): 0 all A, 1 B = inside a dielectric (eta != 1), 2 B = after a specular event
     int dynamic;         // k_extend: waves take 64-path groups from per-shard work counters (KernelCounters::work)
     int shadow_classes;  // shadow rays crossing an enclosing entity's box go to the back of their shard (shadow_class_b)
+    int shadow_optimistic; // k_extend adds a class-A shadow ray's colour to the radiance slot itself and leaves the
+                         // slot's previous value in the record; the shadow kernel restores it if the ray is occluded
     int reverse;         // k_extend: a shard's positions are taken from its end (class C, then B, then A:
                          // the groups whose paths run longest start first, the short ones fill the launch's end)
     int probe_sample;    // test hook (option "probe_sample"): 0 = k_resolve adds every sample; s + 1 = sample s only
@@ -753,10 +758,13 @@ __device__ __forceinline__ void add_aov(float4* A, int slot, f3 c) {
 // per-class counters of the wave's group (`bucket`: camera, A, B, C; lane 0
 // adds the wave's trace / shade cycles, one group, its wave-level node-loop
 // iterations and its lanes' node visits, both reduced over the wave).
+// The radiance (Lacc, has_l) is the caller's to add, as with extend_step: the
+// slot's read-modify-write falls into the store phase (3).
 template <int V>
-__device__ __forceinline__ bool extend_step_instrumented(const FrameArgs& fa, const SceneView& sv, const TStack& ts, float4* L,
-                                                      PathState& ps, bool act, int bucket, bool& has_shadow, ShadowRec& sr,
-                                                      TraceStats& st, unsigned long long& t_last) {
+__device__ __forceinline__ bool extend_step_instrumented(const FrameArgs& fa, const SceneView& sv, const TStack& ts,
+                                                      PathState& ps, bool act, int bucket, f3& Lacc, bool& has_l,
+                                                      bool& has_shadow, ShadowRec& sr, TraceStats& st,
+                                                      unsigned long long& t_last) {
     int hit_ent = -1, hit_prim = -1;
     float hu = 0, hv = 0, tmin = 0, tmax = 0;
     uint32_t rflags = 0;
@@ -787,15 +795,7 @@ __device__ __forceinline__ bool extend_step_instrumented(const FrameArgs& fa, co
     st.t_sub = t_last;
     unsigned long long sub0 = 0;
     for (int k = 0; k < 3; ++k) sub0 += st.cls[20 + 4 * bucket + k];
-    if (act) {
-        f3 Lacc;
-        bool has_l;
-        alive = shade_step<variant_full(V), true>(fa, sv, ps, hit_ent, hit_prim, tmax, hu, hv, Lacc, has_l, has_shadow, sr, &st);
-        if (has_l) {
-            add_radiance(L, ps.slot, Lacc);
-            add_aov<variant_full(V)>(fa.aov_di, ps.slot, Lacc);
-        }
-    }
+    if (act) alive = shade_step<variant_full(V), true>(fa, sv, ps, hit_ent, hit_prim, tmax, hu, hv, Lacc, has_l, has_shadow, sr, &st);
     const unsigned long long c_sh = st.cyc[2];
     phase_mark(st, t_last, 2);
     if (lane_id() == 0) {
@@ -977,49 +977,66 @@ __global__ void __launch_bounds__(BT, LDS ? EXTEND_WAVES_LDS : (variant_full(V0)
         int* const c_sh = kc.cnt_shadow + s * CSTRIDE;
         const int q = p0 + lane_id();
         const int pos = (fa.reverse && !gen) ? ns - 1 - q : q; // reverse: longest classes first
-        bool alive = false, has_shadow = false;
+        bool alive = false, has_shadow = false, has_l = false;
         PathState ps;
         ShadowRec sr;
+        f3 Lacc = mk(0, 0, 0);
         ps.depth = 0;
         if (q < ns) {
             if (gen) { // inverse of gen_index
                 const int i = ((pos >> 6) << 12) | (s << 6) | (pos & 63);
                 ps = camera_path(fa, sv, i);
-                L[i] = make_float4(0, 0, 0, 0);
                 if (variant_full(V0) && IGX_AOV && fa.aov_di) fa.aov_di[i] = fa.aov_nee[i] = make_float4(0, 0, 0, 0);
             } else {
                 ps = load_path(in, path_index(in, s, pos, sc));
             }
-            if (!STATS && ps.depth > 0) {
-                f3 Lacc;
-                bool has_l;
-                alive = extend_step<STATS, V>(fa, sv, ts, ps, Lacc, has_l, has_shadow, sr, st);
-                if (has_l) {
-                    add_radiance(L, ps.slot, Lacc);
-                    add_aov<variant_full(V0)>(fa.aov_di, ps.slot, Lacc);
-                }
-            }
+            if (!STATS && ps.depth > 0) alive = extend_step<STATS, V>(fa, sv, ts, ps, Lacc, has_l, has_shadow, sr, st);
         }
         if constexpr (STATS) {
             // class of the wave's group (wave-uniform): camera, A, B, C
             const int pg = (fa.reverse && !gen) ? ns - 1 - p0 : p0;
             const int bucket = gen ? 0 : (pg < sc.a ? 1 : pg < sc.ab ? 2 : 3);
-            alive = extend_step_instrumented<V>(fa, sv, ts, L, ps, q < ns && ps.depth > 0, bucket, has_shadow, sr, st, t_last);
+            alive = extend_step_instrumented<V>(fa, sv, ts, ps, q < ns && ps.depth > 0, bucket, Lacc, has_l, has_shadow, sr, st, t_last);
         }
+        const bool sh_b = has_shadow && shadow_class_b(fa.shadow_classes, sv, sr.o, sr.d, sr.tmax);
+        // The path's radiance slot takes the emission (has_l) and, with
+        // shadow_optimistic, the colour of a class-A shadow ray in one
+        // read-modify-write: the shadow kernel adds nothing for such a ray and
+        // puts `undo` back if it is occluded (ShadowBuf::s2).  A generated path
+        // (bounce 0) starts from +0 in registers and writes its slot once, dead
+        // and padding paths included (k_generate's zero fill).  The scattered
+        // load goes out ahead of the append's returning atomic and is consumed
+        // behind it: one round trip for both.
+        const bool opt_add = fa.shadow_optimistic && has_shadow && !sh_b;
+        const bool upd = gen ? q < ns : (has_l || opt_add);
+        float4 l = make_float4(0, 0, 0, 0);
+        if (!gen && upd) l = L[ps.slot];
         int dst, sdst;
         // dynamic groups: the append's round trip also takes the next group of
         // shard s, unless s is known exhausted
         int* const claim = (IGX_CLAIM_NEXT && fa.dynamic && !((done >> s) & 1ull)) ? kc.work + s * CSTRIDE : nullptr;
-        wave_append_paths(alive, path_class(fa.classify, sv, ps), has_shadow,
-                          has_shadow && shadow_class_b(fa.shadow_classes, sv, sr.o, sr.d, sr.tmax), c_out, c_sh, out.shard_cap,
+        wave_append_paths(alive, path_class(fa.classify, sv, ps), has_shadow, sh_b, c_out, c_sh, out.shard_cap,
                           out.c_base, sh.shard_cap, dst, sdst, claim, &claimed);
         if (!claim) claimed = -1;
         if (alive) store_path(out, s * out.shard_cap + dst, ps);
+        f3 rec = sr.color; // the shadow record's third word
+        if (upd) {
+            f3 v = f3of(l);
+            if (has_l) {
+                v = mk(v.x + Lacc.x, v.y + Lacc.y, v.z + Lacc.z); // add_radiance
+                add_aov<variant_full(V0)>(fa.aov_di, ps.slot, Lacc);
+            }
+            if (opt_add) {
+                rec = v; // undo
+                v = mk(v.x + sr.color.x, v.y + sr.color.y, v.z + sr.color.z);
+            }
+            L[ps.slot] = make_float4(v.x, v.y, v.z, 0);
+        }
         if (has_shadow) {
             const int e = s * sh.shard_cap + sdst;
             sh.s0[e] = make_float4(sr.o.x, sr.o.y, sr.o.z, __int_as_float(ps.slot));
             sh.s1[e] = make_float4(sr.d.x, sr.d.y, sr.d.z, sr.tmax);
-            sh.s2[e] = make_float4(sr.color.x, sr.color.y, sr.color.z, 0);
+            sh.s2[e] = make_float4(rec.x, rec.y, rec.z, 0);
         }
         if (!fa.dynamic) p0 += w.K * 64;
         if (STATS) phase_mark(st, t_last, 3);
@@ -1340,18 +1357,38 @@ __global__ void __launch_bounds__(BLOCK, FINISH_PAIRS_WAVES) k_finish_pairs(Fram
 // slot (l: the slot's value, loaded before the walk so that the scattered
 // read's latency overlaps the walk: diamond shadow time 20.6 -> 20.3 ms per
 // frame, round 5).  Returns whether the ray is occluded.
+// `undo` (a class-A lane of a group with both classes under
+// ShadowBuf::optimistic, see shadow_walk_undo): col is the slot's previous
+// value, stored back if the ray is occluded; l is not used.
 template <bool STATS, int V>
 __device__ __forceinline__ bool shadow_walk(const SceneView& sv, const TStack& ts, float4 s0, float4 s1, float4 col, float4 l,
-                                            float4* L, float4* aov_nee, TraceStats& st) {
+                                            bool undo, float4* L, float4* aov_nee, TraceStats& st) {
     float tmax = s1.w;
     int e, p;
     float u, v;
     const bool occl = trace_ray<true, STATS, V>(sv, f3of(s0), f3of(s1), 0.001f, tmax, RAY_SHADOW, ts, e, p, u, v, st);
-    if (!occl) {
-        const int slot = __float_as_int(s0.w);
+    const int slot = __float_as_int(s0.w);
+    if (undo) {
+        if (occl) L[slot] = make_float4(col.x, col.y, col.z, 0);
+    } else if (!occl) {
         L[slot] = make_float4(l.x + col.x, l.y + col.y, l.z + col.z, 0); // add_radiance
         add_aov(aov_nee, slot, f3of(col));
     }
+    return occl;
+}
+// A class-A ray under ShadowBuf::optimistic: k_extend added its colour
+// already, so an unoccluded ray (99.9 % of them on the diamond frame) touches
+// neither its slot nor the record's third word; an occluded one stores the
+// slot's previous value back (s2: the undo value).  The caller takes this
+// path for a wave whose whole group is class A.
+template <bool STATS, int V>
+__device__ __forceinline__ bool shadow_walk_undo(const SceneView& sv, const TStack& ts, float4 s0, float4 s1, const float4* undo,
+                                                 float4* L, TraceStats& st) {
+    float tmax = s1.w;
+    int e, p;
+    float u, v;
+    const bool occl = trace_ray<true, STATS, V>(sv, f3of(s0), f3of(s1), 0.001f, tmax, RAY_SHADOW, ts, e, p, u, v, st);
+    if (occl) L[__float_as_int(s0.w)] = *undo;
     return occl;
 }
 
@@ -1421,9 +1458,15 @@ __global__ void __launch_bounds__(BLOCK) k_shadow(SceneView gsv, ShadowBuf sh, f
             const int pos = p0 + lane;
             stats_begin();
             bool occl = false;
-            if (pos < sc.n) {
+            if (sh.optimistic && p0 + 63 < sc.a) { // a whole group of class A (wave-uniform): the lean path
+                const int i = s * sh.shard_cap + pos;
+                occl = shadow_walk_undo<STATS, V>(sv, ts, sh.s0[i], sh.s1[i], sh.s2 + i, L, st);
+            } else if (pos < sc.n) {
                 const int i = stream_index(s, pos, sc.a, sh.shard_cap);
-                occl = shadow_walk<STATS, V>(sv, ts, sh.s0[i], sh.s1[i], sh.s2[i], L[__float_as_int(sh.s0[i].w)], L, sh.aov_nee, st);
+                const bool undo = sh.optimistic && pos < sc.a; // class-A lanes of the shard's one group with both classes
+                const float4 s0 = sh.s0[i];
+                const float4 l = undo ? make_float4(0, 0, 0, 0) : L[__float_as_int(s0.w)];
+                occl = shadow_walk<STATS, V>(sv, ts, s0, sh.s1[i], sh.s2[i], l, undo, L, sh.aov_nee, st);
             }
             stats_end(p0, pos < sc.n, occl);
         }
@@ -1475,7 +1518,11 @@ __global__ void __launch_bounds__(BLOCK) k_shadow(SceneView gsv, ShadowBuf sh, f
 // refill takes at most 64 positions).  All members are wave-uniform.
 // CLASSES: the stream holds two path classes (stream_index); otherwise
 // position pos of shard s is stored at s * shard_cap + pos.
-template <bool CLASSES>
+// TAG_A: at() sets the sign bit of a class-A position's stream index
+// (CLASS_A_TAG; indices stay below 2^31), so the lane's finish step knows the
+// class without a register of its own.
+constexpr int CLASS_A_TAG = (int)0x80000000u;
+template <bool CLASSES, bool TAG_A = false>
 struct GroupSeq {
     const int* cnt;
     int* work;
@@ -1550,7 +1597,9 @@ struct GroupSeq {
         const int pos = g * 64 + (c & 63);
         if (pos >= (k ? gn[1] : gn[0])) return false;
         const int sh = k ? gs[1] : gs[0];
-        i = CLASSES ? stream_index(sh, pos, k ? ga[1] : ga[0], shard_cap) : sh * shard_cap + pos;
+        const int a = k ? ga[1] : ga[0];
+        i = CLASSES ? stream_index(sh, pos, a, shard_cap) : sh * shard_cap + pos;
+        if (TAG_A && pos < a) i |= CLASS_A_TAG;
         return true;
     }
 };
@@ -1608,21 +1657,31 @@ __global__ void __launch_bounds__(BLOCK, LDS ? REFILL_WAVES_LDS : (variant_ifif(
     if (row_total(cnt) == 0) return;
     const SceneView sv = LDS ? stage_scene_lds<BLOCK>(gsv, lds_scene) : stage_treelet<BLOCK>(gsv, lds_scene);
     TraceStats st{0, 0, 0, 0, 0, 0, 0};
-    GroupSeq<true> seq; // two shadow classes (wave_append_paths)
+    GroupSeq<true, true> seq; // two shadow classes (wave_append_paths), class-A indices tagged
     seq.init(cnt, work, sh.shard_cap, wave_work());
     refill_loop<true, STATS, V>(
         sv, ts, seq, refill_min,
-        [&](int i, Trav& t) -> bool {
+        [&](int it, Trav& t) -> bool {
+            const int i = it & ~CLASS_A_TAG;
             const float4 s0 = sh.s0[i], s1 = sh.s1[i];
             trav_init(sv, t, f3of(s0), f3of(s1), 0.001f, s1.w, RAY_SHADOW, ts);
             return true;
         },
-        [&](int i, const Trav& t) {
-            if (t.found) return;
+        [&](int it, const Trav& t) {
+            // a class-A record under ShadowBuf::optimistic: k_extend added the
+            // colour, an occluded ray puts the slot's previous value back (s2);
+            // any other record: an unoccluded ray adds its colour
+            const bool undo = sh.optimistic && it < 0;
+            if (t.found != undo) return;
+            const int i = it & ~CLASS_A_TAG;
             const int slot = __float_as_int(sh.s0[i].w);
-            const f3 col = f3of(sh.s2[i]);
-            add_radiance(L, slot, col);
-            add_aov(sh.aov_nee, slot, col);
+            const float4 rec = sh.s2[i];
+            if (undo) {
+                L[slot] = rec;
+                return;
+            }
+            add_radiance(L, slot, f3of(rec));
+            add_aov(sh.aov_nee, slot, f3of(rec));
         },
         st);
     if (STATS) flush_stats<STATS>(st, stats, 4, false);
@@ -1992,6 +2051,11 @@ struct igx_device {
     // entity's box apart from the rest (shadow_class_b), 0/1: diamond shadow
     // time 26.9 -> 21.7 ms per frame, frame 121.1 -> 118.4 ms, bit-identical
     int shadow_classes_opt = 1;
+    // option "shadow_optimistic" (-1 auto, 0 off, 1 on; use_shadow_optimistic):
+    // k_extend adds a class-A shadow ray's colour to the radiance slot itself,
+    // the shadow kernel only undoes it for the occluded ones (FrameArgs::
+    // shadow_optimistic; bit-identical)
+    int shadow_optimistic_opt = -1;
     // option "dynamic" (DYN_* bits): DYN_EXTEND = k_extend waves take their
     // groups of 64 paths from per-shard counters (take_group) instead of a
     // fixed grid stride: diamond frame 142.4 -> 134.3 ms, materials 66.5 ->
@@ -2282,6 +2346,16 @@ inline bool use_split(const igx_device* dev) {
 // loop is faster.  Option "shadow_ifif": -1 auto, 0 off, 1 on.
 inline bool use_shadow_ifif(const igx_device* dev) {
     return dev->shadow_ifif_opt >= 0 ? dev->shadow_ifif_opt != 0 : use_split(dev);
+}
+// k_extend adds class-A shadow colours itself and the shadow kernel undoes the
+// occluded ones (option "shadow_optimistic": -1 auto, 0 off, 1 on).  Only on
+// the fused schedule (k_shade is left as it is) and without the MIS AOVs
+// ("NEE Weights" needs the colour in the record); auto also asks for shadow
+// classes and an enclosing entity, which give class A its meaning (rays that
+// are almost never occluded), 1 takes every front-of-shard record.
+inline bool use_shadow_optimistic(const igx_device* dev, bool split, bool aovs) {
+    if (dev->shadow_optimistic_opt == 0 || split || aovs) return false;
+    return dev->shadow_optimistic_opt > 0 || (dev->shadow_classes_opt && dev->sv.num_enc > 0);
 }
 
 // Launch helpers dispatching on the scene's traversal variant.
@@ -2972,6 +3046,10 @@ extern "C" igx_status igx_set_option(igx_device* dev, const char* key, int64_t v
     else if (k == "shadow_ifif") {
         if (value < -1 || value > 1) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "shadow_ifif must be -1 (auto), 0 or 1");
         dev->shadow_ifif_opt = (int)value;
+    }
+    else if (k == "shadow_optimistic") {
+        if (value < -1 || value > 1) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "shadow_optimistic must be -1 (auto), 0 or 1");
+        dev->shadow_optimistic_opt = (int)value;
     }
     else if (k == "refill") {
         if (value < -1 || value > 64) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "refill must be -1 (auto) or in [0, 64]");
@@ -4011,6 +4089,7 @@ igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
             r.fa.aov_di = dev->aov_on && dev->aov_fb[0] ? S.aov_di : nullptr;
             r.fa.aov_nee = dev->aov_on && dev->aov_fb[1] ? S.aov_nee : nullptr;
             S.sh.aov_nee = r.fa.aov_nee;
+            S.sh.optimistic = r.fa.shadow_optimistic;
             r.fa.iter = pl.iteration + r.it0;
             r.fa.chunk_iters = std::min(pl.iters_per_chunk, pl.count - r.it0);
             r.chunk_pixels = (int)std::min<long long>(pl.chunk_pixels_max, pl.local_pixels - r.px0);
@@ -4400,6 +4479,7 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
     fa.inv_spi = 1.0f / (float)p->spi;
     fa.classify = dev->classify_opt;
     fa.shadow_classes = dev->shadow_classes_opt;
+    fa.shadow_optimistic = use_shadow_optimistic(dev, split, dev->aov_on && !list_mode);
     fa.dynamic = dev->dynamic_opt & DYN_EXTEND;
     fa.reverse = fa.dynamic ? (dev->group_order_opt < 0 ? GROUP_ORDER_AUTO : dev->group_order_opt) : 0;
     fa.probe_sample = dev->probe_sample_opt > 0 && dev->probe_sample_opt <= p->spi ? (int)dev->probe_sample_opt : 0;
@@ -4557,6 +4637,7 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
         fa.aov_di = dev->aov_on && dev->aov_fb[0] && !list_mode ? S.aov_di : nullptr;
         fa.aov_nee = dev->aov_on && dev->aov_fb[1] && !list_mode ? S.aov_nee : nullptr;
         S.sh.aov_nee = fa.aov_nee;
+        S.sh.optimistic = fa.shadow_optimistic;
 
         auto begin_timed = [&](int kind, int bounce, hipStream_t strm) {
             if (!dev->timing) return;
