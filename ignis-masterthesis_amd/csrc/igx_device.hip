@@ -30,6 +30,7 @@
 #include "../host/bvh_build.h"
 #include "../host/light_select.h"
 #include "../host/lds_plan.h"
+#include "../host/extend_shape.h"
 #include "../host/aov_plan.h"
 #include "../host/film_tools.h"
 
@@ -58,7 +59,9 @@ using namespace igxd;
 //   2 = k_finish variants; 3 = k_trace / k_trace_refill / k_shade / k_shadow /
 //   k_shadow_refill variants; 4 = the wide (BLOCK_WIDE-thread) k_extend variants;
 //   5 = the k_infobuffer variants; 6 = the film post-processing kernels
-//   (igx_post.h).  Types and device functions are shared; each
+//   (igx_post.h); 7 = the wide k_extend's generate and bounce shapes
+//   (host/extend_shape.h); 8, 9 = the two shapes of the BLOCK-thread k_extend
+//   with LDS-staged and with global tables.  Types and device functions are shared; each
 //   part instantiates only its own launch helpers (explicit instantiation),
 //   the others see them as extern templates.
 #ifndef IGX_PART
@@ -919,10 +922,48 @@ __device__ __forceinline__ PathState camera_path(const FrameArgs& fa, const Scen
 // ---------------------------------------------------------------------------
 // BT threads per block: BLOCK, or BLOCK_WIDE for the LDS-staged kernel with
 // the shading tables staged too (16 waves, 4 per SIMD: the same 128-VGPR cap).
-template <int V0, bool STATS, bool LDS, int BT = BLOCK>
-__global__ void __launch_bounds__(BT, LDS ? EXTEND_WAVES_LDS : (variant_full(V0) ? EXTEND_WAVES_FULL : EXTEND_WAVES)) k_extend(FrameArgs fa, SceneView gsv, PathBuf in, PathBuf out, ShadowBuf sh,
+// SHAPE (host/extend_shape.h, chosen per launch by pick_extend_shape): the
+// generate and bounce shapes fold the default fused mode's flags to constants
+// (dynamic groups, front-to-back order, three path classes, shadow classes,
+// no ray list, no MIS AOVs) and drop the other half of the generate / load
+// branch, so those values leave the group loop's live set; the arithmetic of
+// a path is the generic kernel's.
+template <int V0, bool STATS, bool LDS, int BT = BLOCK, int SHAPE = EXTEND_GENERIC>
+__global__ void __launch_bounds__(BT, LDS ? EXTEND_WAVES_LDS : (variant_full(V0) ? EXTEND_WAVES_FULL : EXTEND_WAVES)) k_extend(FrameArgs fa_arg, SceneView gsv, PathBuf in, PathBuf out, ShadowBuf sh,
                                                   float4* L, KernelCounters kc, int tail_threshold) {
     static_assert(BT == BLOCK || (LDS && BT == BLOCK_WIDE), "the wide block is the LDS-staged kernel's");
+    static_assert(SHAPE == EXTEND_GENERIC || !STATS, "the instrumented kernel is generic");
+    FrameArgs fa = fa_arg;
+    if constexpr (SHAPE != EXTEND_GENERIC) {
+        fa.dynamic = 1;
+        fa.reverse = 0;
+        fa.classify = EXTEND_SHAPE_CLASSIFY;
+        fa.shadow_classes = 1;
+        fa.num_rays = 0;
+        fa.rays = nullptr;
+        fa.aov_di = fa.aov_nee = nullptr;
+        if constexpr (SHAPE == EXTEND_BOUNCE) fa.gen_n = 0;
+        // pointer families from one base each (the host checked the layout,
+        // streams_packed): both path buffers and the shadow stream share the
+        // shard capacity, a path buffer holds the class-C region behind its
+        // shards, and the three counter rows of a bounce are neighbours
+        const int cap = out.shard_cap;
+        const size_t recs = (size_t)NSH * cap;
+        auto derive = [&](PathBuf& b) {
+            b.shard_cap = cap;
+            b.c_base = NSH * cap;
+            b.p1 = b.p0 + 2 * recs;
+            b.p2 = b.p0 + 4 * recs;
+            b.p3 = reinterpret_cast<float2*>(b.p0 + 6 * recs);
+        };
+        derive(out);
+        if constexpr (SHAPE == EXTEND_BOUNCE) derive(in);
+        sh.shard_cap = cap;
+        sh.s1 = sh.s0 + recs;
+        sh.s2 = sh.s0 + 2 * recs;
+        kc.cnt_shadow = kc.cnt_in + CROW;
+        kc.cnt_out = kc.cnt_in + 2 * CROW;
+    }
     constexpr bool SHADE_LDS = BT > BLOCK; // the wide block stages the shading tables too
     constexpr int V = LDS ? kernel_variant(V0, true) : (EXTEND_TREELET ? kernel_variant(V0, false) : V0); // LDS-staged tables: bit 3 (node steps skip the stack-top peek); global tables: treelet (device_scene.h) or global node loads
     __shared__ int stack_mem[LDS_STACK * BT];
@@ -931,7 +972,7 @@ __global__ void __launch_bounds__(BT, LDS ? EXTEND_WAVES_LDS : (variant_full(V0)
     // gen_n > 0 (bounce 0 with generation fused; the host launches it only
     // when n > tail): the paths are the chunk's camera paths in k_generate's
     // shard order, built here instead of being read from the input stream.
-    const bool gen = fa.gen_n > 0;
+    const bool gen = SHAPE == EXTEND_GENERATE ? true : SHAPE == EXTEND_BOUNCE ? false : fa.gen_n > 0;
     if (!gen && row_total(kc.cnt_in) <= tail_threshold) return; // k_finish takes the remaining paths (block-uniform)
     const SceneView sv = LDS ? stage_scene_lds<BT, SHADE_LDS>(gsv, lds_scene) : stage_treelet<BT>(gsv, lds_scene);
     TraceStats st{0, 0, 0, 0, 0, 0, 0};
@@ -2056,6 +2097,11 @@ struct igx_device {
     // the shadow kernel only undoes it for the occluded ones (FrameArgs::
     // shadow_optimistic; bit-identical)
     int shadow_optimistic_opt = -1;
+    // option "extend_shapes" (-1 auto, 0 generic only, 1 specialised where
+    // eligible; pick_extend_shape, host/extend_shape.h): launches of the
+    // default fused mode run k_extend's generate / bounce shapes
+    // (bit-identical)
+    int extend_shapes_opt = -1;
     // option "dynamic" (DYN_* bits): DYN_EXTEND = k_extend waves take their
     // groups of 64 paths from per-shard counters (take_group) instead of a
     // fixed grid stride: diamond frame 142.4 -> 134.3 ms, materials 66.5 ->
@@ -2233,8 +2279,8 @@ igx_status configure_stack(igx_device* dev) {
 }
 
 void free_slot_buffers(Slot& s) {
-    void* ptrs[] = {s.pa.p0, s.pa.p1, s.pa.p2, s.pa.p3, s.pb.p0, s.pb.p1, s.pb.p2, s.pb.p3, s.sh.s0, s.sh.s1, s.sh.s2, s.L, s.hb.h, s.hb.prim,
-                    s.aov_di, s.aov_nee};
+    // a path buffer's four arrays and the shadow stream's three are one block each (ensure_slot)
+    void* ptrs[] = {s.pa.p0, s.pb.p0, s.sh.s0, s.L, s.hb.h, s.hb.prim, s.aov_di, s.aov_nee};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     s.pa = PathBuf{};
@@ -2268,12 +2314,19 @@ igx_status ensure_slot(igx_device* dev, Slot& s, size_t cap, bool hits, bool reg
     auto alloc4 = [&](float4** p, size_t k) -> igx_status { HIPCHK(hipMalloc((void**)p, k * sizeof(float4))); return IGX_OK; };
     igx_status st;
     const size_t precs = region_c ? 2 * recs : recs;
-    if ((st = alloc4(&s.pa.p0, precs)) || (st = alloc4(&s.pa.p1, precs)) || (st = alloc4(&s.pa.p2, precs))) return st;
-    HIPCHK(hipMalloc((void**)&s.pa.p3, precs * sizeof(float2)));
-    if ((st = alloc4(&s.pb.p0, precs)) || (st = alloc4(&s.pb.p1, precs)) || (st = alloc4(&s.pb.p2, precs))) return st;
-    HIPCHK(hipMalloc((void**)&s.pb.p3, precs * sizeof(float2)));
+    // One block per stream, its arrays back to back (p0, p1, p2, then p3; s0,
+    // s1, s2): k_extend's shapes derive the arrays from the first pointer and
+    // the shard capacity (streams_packed, host/extend_shape.h)
+    for (PathBuf* b : {&s.pa, &s.pb}) {
+        HIPCHK(hipMalloc((void**)&b->p0, precs * (3 * sizeof(float4) + sizeof(float2))));
+        b->p1 = b->p0 + precs;
+        b->p2 = b->p0 + 2 * precs;
+        b->p3 = reinterpret_cast<float2*>(b->p0 + 3 * precs);
+    }
     s.pa.c_base = s.pb.c_base = region_c ? (int)recs : 0;
-    if ((st = alloc4(&s.sh.s0, recs)) || (st = alloc4(&s.sh.s1, recs)) || (st = alloc4(&s.sh.s2, recs))) return st;
+    if ((st = alloc4(&s.sh.s0, 3 * recs))) return st;
+    s.sh.s1 = s.sh.s0 + recs;
+    s.sh.s2 = s.sh.s0 + 2 * recs;
     if ((st = alloc4(&s.L, cap))) return st; // radiance is indexed by path slot, not sharded
     if (aov && ((st = alloc4(&s.aov_di, cap)) || (st = alloc4(&s.aov_nee, cap)))) return st;
     if (hits) {
@@ -2424,9 +2477,101 @@ hipError_t extend_wide_prepare(int v, size_t dyn) {
     return hipSuccess;
 }
 
+// The generate and bounce shapes of k_extend (host/extend_shape.h), one part
+// per LDS layout: the wide block (part 7), the BLOCK-thread kernel with
+// LDS-staged tables (part 8) and with global tables (part 9).  They share
+// launch bounds and static LDS with the generic instantiation of their
+// layout, so grids and the treelet are sized by the generic kernel's
+// resident blocks.
+void launch_extend_shaped_wide(igx_device* dev, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa, const PathBuf& in,
+                               const PathBuf& out, const KernelCounters& kc, int tail);
+hipError_t extend_shaped_wide_prepare(int v, size_t dyn);
+void launch_extend_shaped_lds(igx_device* dev, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa, const PathBuf& in,
+                              const PathBuf& out, const KernelCounters& kc, int tail);
+void launch_extend_shaped_global(igx_device* dev, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa, const PathBuf& in,
+                                 const PathBuf& out, const KernelCounters& kc, int tail);
+#define IGX_SHAPED(S, LDS_, BT_, dyn_, sv_)                                                                                        \
+    if (shape == EXTEND_GENERATE)                                                                                                  \
+        hipLaunchKernelGGL((k_extend<S, false, LDS_, BT_, EXTEND_GENERATE>), dim3(grid), dim3(BT_), dyn_, dev->stream, fa, sv_, in, \
+                           out, s.sh, s.L, kc, tail);                                                                              \
+    else                                                                                                                           \
+        hipLaunchKernelGGL((k_extend<S, false, LDS_, BT_, EXTEND_BOUNCE>), dim3(grid), dim3(BT_), dyn_, dev->stream, fa, sv_, in,   \
+                           out, s.sh, s.L, kc, tail)
+#if IGX_PART == 7
+void launch_extend_shaped_wide(igx_device* dev, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa, const PathBuf& in,
+                               const PathBuf& out, const KernelCounters& kc, int tail) {
+    const size_t dyn = lds_pad16(dev->lds_scene_bytes) + dev->lds_shading_bytes;
+#define L_EXTW(S) IGX_SHAPED(S, true, BLOCK_WIDE, dyn, dev->sv)
+    IGX_DISPATCH_VARIANT8(dev->variant, L_EXTW);
+#undef L_EXTW
+}
+hipError_t extend_shaped_wide_prepare(int v, size_t dyn) {
+#define L_PREP(S)                                                                                           \
+    {                                                                                                       \
+        const hipError_t e = raise_dynamic_lds(k_extend<S, false, true, BLOCK_WIDE, EXTEND_GENERATE>, dyn); \
+        return e != hipSuccess ? e : raise_dynamic_lds(k_extend<S, false, true, BLOCK_WIDE, EXTEND_BOUNCE>, dyn); \
+    }
+    IGX_DISPATCH_VARIANT8(v, L_PREP);
+#undef L_PREP
+    return hipSuccess;
+}
+#endif
+#if IGX_PART == 8
+void launch_extend_shaped_lds(igx_device* dev, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa, const PathBuf& in,
+                              const PathBuf& out, const KernelCounters& kc, int tail) {
+#define L_EXTL(S) IGX_SHAPED(S, true, BLOCK, dev->lds_scene_bytes, dev->sv)
+    IGX_DISPATCH_VARIANT8(dev->variant, L_EXTL);
+#undef L_EXTL
+}
+#endif
+#if IGX_PART == 9
+void launch_extend_shaped_global(igx_device* dev, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa, const PathBuf& in,
+                                 const PathBuf& out, const KernelCounters& kc, int tail) {
+    SceneView tsv = dev->sv;
+    tsv.tree_n = dev->tree_ext;
+#define L_EXT(S) IGX_SHAPED(S, false, BLOCK, tree_bytes(dev, tsv.tree_n), tsv)
+    IGX_DISPATCH_VARIANT8(dev->variant, L_EXT);
+#undef L_EXT
+}
+#endif
+#undef IGX_SHAPED
+
+// The shape of one k_extend launch: a pure function of the options and the
+// launch's FrameArgs (pick_extend_shape, host/extend_shape.h)
+inline ExtendShape launch_shape(const igx_device* dev, bool instrumented, const FrameArgs& fa, const PathBuf& pin, const PathBuf& out,
+                                const ShadowBuf& sh, const KernelCounters& kc) {
+    ExtendShapeInput in;
+    in.extend_shapes = dev->extend_shapes_opt;
+    in.instrument = instrumented;
+    in.gen_n = fa.gen_n;
+    in.dynamic = fa.dynamic;
+    in.reverse = fa.reverse;
+    in.classify = fa.classify;
+    in.shadow_classes = fa.shadow_classes;
+    in.num_rays = fa.num_rays;
+    in.mis_aovs = fa.aov_di != nullptr || fa.aov_nee != nullptr;
+    // the layout the shapes derive their pointers from (k_extend)
+    const auto packed = [&](const PathBuf& b) {
+        const size_t recs = (size_t)NSH * b.shard_cap;
+        return b.shard_cap == out.shard_cap && b.c_base == NSH * b.shard_cap && b.p1 == b.p0 + 2 * recs && b.p2 == b.p0 + 4 * recs &&
+               b.p3 == reinterpret_cast<const float2*>(b.p0 + 6 * recs);
+    };
+    const size_t srecs = (size_t)NSH * sh.shard_cap;
+    in.streams_packed = packed(pin) && packed(out) && sh.shard_cap == out.shard_cap && sh.s1 == sh.s0 + srecs && sh.s2 == sh.s0 + 2 * srecs &&
+                        kc.cnt_shadow == kc.cnt_in + CROW && kc.cnt_out == kc.cnt_in + 2 * CROW;
+    return pick_extend_shape(in);
+}
+
 template <bool STATS>
 void launch_extend(igx_device* dev, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in, const PathBuf& out,
                    const KernelCounters& kc, int tail) {
+    if (const ExtendShape shape = launch_shape(dev, STATS, fa, in, out, s.sh, kc); shape != EXTEND_GENERIC) {
+        ++dev->stats.launches_extend_shaped[shape == EXTEND_GENERATE ? 0 : 1];
+        if (dev->ext_block == BLOCK_WIDE) launch_extend_shaped_wide(dev, s, grid, shape, fa, in, out, kc, tail);
+        else if (dev->lds_scene_bytes) launch_extend_shaped_lds(dev, s, grid, shape, fa, in, out, kc, tail);
+        else launch_extend_shaped_global(dev, s, grid, shape, fa, in, out, kc, tail);
+        return;
+    }
     if (dev->ext_block == BLOCK_WIDE) {
         launch_extend_wide<STATS>(dev, s, grid, fa, in, out, kc, tail);
         return;
@@ -2793,6 +2938,7 @@ void configure_lds(igx_device* dev) {
         (void)hipSetDevice(dev->hip_device);
         hipError_t e = extend_wide_prepare<false>(dev->variant, dyn);
         if (e == hipSuccess) e = extend_wide_prepare<true>(dev->variant, dyn);
+        if (e == hipSuccess) e = extend_shaped_wide_prepare(dev->variant, dyn);
         if (e != hipSuccess) {
             (void)hipGetLastError();
             dev->last_error = std::string("lds_shading: the wide k_extend's LDS block was refused (") + hipGetErrorString(e) +
@@ -3050,6 +3196,10 @@ extern "C" igx_status igx_set_option(igx_device* dev, const char* key, int64_t v
     else if (k == "shadow_optimistic") {
         if (value < -1 || value > 1) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "shadow_optimistic must be -1 (auto), 0 or 1");
         dev->shadow_optimistic_opt = (int)value;
+    }
+    else if (k == "extend_shapes") {
+        if (value < -1 || value > 1) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "extend_shapes must be -1 (auto), 0 or 1");
+        dev->extend_shapes_opt = (int)value;
     }
     else if (k == "refill") {
         if (value < -1 || value > 64) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "refill must be -1 (auto) or in [0, 64]");

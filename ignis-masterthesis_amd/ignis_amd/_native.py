@@ -136,7 +136,8 @@ class Stats(C.Structure):
                 ("shadow_class_occluded", C.c_uint64 * 2), ("tlas_node_visits", C.c_uint64),
                 ("hot_node_visits", C.c_uint64 * 3), ("extend_class_shade_cycles", C.c_uint64 * 16),
                 ("shadow_class_rays", C.c_uint64 * 2),
-                ("lds_shading_bytes", C.c_int32), ("extend_block_threads", C.c_int32)]
+                ("lds_shading_bytes", C.c_int32), ("extend_block_threads", C.c_int32),
+                ("launches_extend_shaped", C.c_uint64 * 2)]
 
     def as_dict(self):
         return {name: (list(getattr(self, name)) if isinstance(getattr(self, name), C.Array) else getattr(self, name))
