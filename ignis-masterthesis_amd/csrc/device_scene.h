@@ -83,7 +83,9 @@ struct DevMaterial {   // 128 B
 };
 
 enum : int32_t { LIGHT_PLANE = 1, LIGHT_ENV = 2, LIGHT_POINT = 3, LIGHT_SPOT = 4, LIGHT_DIRECTIONAL = 5, LIGHT_SUN = 6,
-                   LIGHT_SPHERE = 7, LIGHT_MESH = 8 };
+                   LIGHT_SPHERE = 7, LIGHT_MESH = 8, LIGHT_CIE = 9 };
+// A CIE sky (LIGHT_CIE, host/cie_sky.h) keeps its CieSky record in the 28
+// floats from `radiance` on (cie_sky_of); `entity` is unused.
 struct DevLight {      // 128 B
     int32_t type, infinite, delta, entity; // entity: emitting entity of sphere / mesh area lights
     float radiance[4];
@@ -96,10 +98,7 @@ struct DevLight {      // 128 B
     float pad2[4];
 };
 
-struct DevCamera {
-    float eye[3], dir[3], up[3], right[3];
-    float scale_x, scale_y;
-    float tmin, tmax;
-};
-
 } // namespace igxd
+
+// DevCamera and the camera models' ray arithmetic (shared with the host)
+#include "../host/camera_model.h"

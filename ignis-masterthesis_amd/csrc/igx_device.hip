@@ -41,6 +41,7 @@
 #include <chrono>
 #include <map>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <condition_variable>
 #include <deque>
@@ -61,7 +62,8 @@ using namespace igxd;
 //   5 = the k_infobuffer variants; 6 = the film post-processing kernels
 //   (igx_post.h); 7 = the wide k_extend's generate and bounce shapes
 //   (host/extend_shape.h); 8, 9 = the two shapes of the BLOCK-thread k_extend
-//   with LDS-staged and with global tables.  Types and device functions are shared; each
+//   with LDS-staged and with global tables; 10 = k_camera_rays (igx_camera_rays).
+//   Types and device functions are shared; each
 //   part instantiates only its own launch helpers (explicit instantiation),
 //   the others see them as extern templates.
 #ifndef IGX_PART
@@ -367,6 +369,13 @@ struct GenPath {
     uint32_t counter, seed;
     int depth;
 };
+// FULL (the full shading variant) goes through camera_ray (host/camera_model.h:
+// every camera model; the depth-of-field camera draws its two lens numbers
+// after the jitter).  The basic variant keeps the pinhole perspective camera's
+// own statement, so its kernels are the ones they were before the other models
+// came; camera_ray's pinhole branch is the same arithmetic (a GPU test compares
+// the two bit for bit).
+template <bool FULL>
 __device__ __forceinline__ GenPath gen_path(const FrameArgs& fa, const SceneView& sv, int i) {
     int lp, sample, iter;
     slot_coords(fa, i, lp, sample, iter);
@@ -386,33 +395,73 @@ __device__ __forceinline__ GenPath gen_path(const FrameArgs& fa, const SceneView
             float ry = rnd.next_f32();
             float nx = 2 * ((float)x + rx) / (float)fa.width - 1;
             float ny = 1 - 2 * ((float)y + ry) / (float)fa.height;
-            const DevCamera& c = sv.cam;
-            f3 v = mk(c.scale_x * nx, c.scale_y * ny, 1);
-            f3 w = mk(c.right[0] * v.x + c.up[0] * v.y + c.dir[0] * v.z,
-                      c.right[1] * v.x + c.up[1] * v.y + c.dir[1] * v.z,
-                      c.right[2] * v.x + c.up[2] * v.y + c.dir[2] * v.z);
-            g.o = mk(c.eye[0], c.eye[1], c.eye[2]);
-            g.d = normalize(w);
+            if constexpr (FULL) {
+                const DevLens lens{sv.cam_type, sv.cam_aperture, sv.cam_focal};
+                float lu = 0, lv = 0;
+                if (camera_has_dof(lens)) {
+                    lu = rnd.next_f32();
+                    lv = rnd.next_f32();
+                }
+                CamVec o, d;
+                camera_ray(sv.cam, lens, nx, ny, lu, lv, o, d);
+                g.o = mk(o.x, o.y, o.z);
+                g.d = mk(d.x, d.y, d.z);
+            } else {
+                const DevCamera& c = sv.cam;
+                f3 v = mk(c.scale_x * nx, c.scale_y * ny, 1);
+                f3 w = mk(c.right[0] * v.x + c.up[0] * v.y + c.dir[0] * v.z,
+                          c.right[1] * v.x + c.up[1] * v.y + c.dir[1] * v.z,
+                          c.right[2] * v.x + c.up[2] * v.y + c.dir[2] * v.z);
+                g.o = mk(c.eye[0], c.eye[1], c.eye[2]);
+                g.d = normalize(w);
+            }
         }
         g.counter = rnd.counter;
     }
     return g;
 }
 
+#if IGX_PART == 10
+// The camera rays of one sample of every pixel (igx_camera_rays): one lane
+// per pixel, grid-stride, through gen_path, so the rays are the renderer's.
+// `fa` describes one chunk of the whole film at spi = sample + 1, so slot
+// lp * spi + sample is that sample of local pixel lp.  Row-major, 8 floats
+// per pixel: org, dir, tmin, tmax.
+__global__ void __launch_bounds__(BLOCK) k_camera_rays(FrameArgs fa, SceneView sv, float4* rays) {
+    const int sample = fa.spi - 1;
+    for (int lp = blockIdx.x * BLOCK + threadIdx.x; lp < fa.chunk_pixels; lp += gridDim.x * BLOCK) {
+        int x, y;
+        if (!local_to_global(fa, lp, x, y)) continue;
+        const GenPath g = gen_path<true>(fa, sv, lp * fa.spi + sample);
+        const size_t p = (size_t)y * fa.width + x;
+        rays[2 * p] = make_float4(g.o.x, g.o.y, g.o.z, g.d.x);
+        rays[2 * p + 1] = make_float4(g.d.y, g.d.z, sv.cam.tmin, sv.cam.tmax);
+    }
+}
+#endif
+
 #if IGX_PART == 0
-__global__ void __launch_bounds__(BLOCK) k_generate(FrameArgs fa, SceneView sv, PathBuf out, float4* L, int* cnt0) {
+template <bool FULL>
+__device__ __forceinline__ void generate_paths(const FrameArgs& fa, const SceneView& sv, const PathBuf& out, float4* L, int* cnt0) {
     const int n = fa.chunk_pixels * fa.spi * fa.chunk_iters;
     if (blockIdx.x == 0 && threadIdx.x < NSH) cnt0[threadIdx.x * CSTRIDE] = gen_shard_count(n, threadIdx.x);
     for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
         L[i] = make_float4(0, 0, 0, 0);
         if (IGX_AOV && fa.aov_di) fa.aov_di[i] = fa.aov_nee[i] = make_float4(0, 0, 0, 0);
-        const GenPath g = gen_path(fa, sv, i);
+        const GenPath g = gen_path<FULL>(fa, sv, i);
         const int e = gen_index(i, out.shard_cap);
         out.p0[e] = make_float4(g.o.x, g.o.y, g.o.z, __int_as_float(i));
         out.p1[e] = make_float4(g.d.x, g.d.y, g.d.z, __uint_as_float(g.counter | ((uint32_t)g.depth << 24)));
         out.p2[e] = make_float4(1, 1, 1, 0); // init_pt_raypayload (technique/pathtracer.art:33-38)
         out.p3[e] = make_float2(1.0f, __uint_as_float(g.seed));
     }
+}
+// the basic and the full shading variant's camera models (gen_path)
+__global__ void __launch_bounds__(BLOCK) k_generate(FrameArgs fa, SceneView sv, PathBuf out, float4* L, int* cnt0) {
+    generate_paths<false>(fa, sv, out, L, cnt0);
+}
+__global__ void __launch_bounds__(BLOCK) k_generate_full(FrameArgs fa, SceneView sv, PathBuf out, float4* L, int* cnt0) {
+    generate_paths<true>(fa, sv, out, L, cnt0);
 }
 
 #endif
@@ -617,6 +666,8 @@ __device__ __forceinline__ bool shade_step(const FrameArgs& fa, const SceneView&
             if (Lt.delta) continue;
             f3 emit = mk(Lt.radiance[0], Lt.radiance[1], Lt.radiance[2]);
             float pdf_s = 1 / (4 * PI_);
+            if constexpr (FULL)
+                if (Lt.type == LIGHT_CIE) cie_emission(Lt, rd, emit, pdf_s);
             const float sel = sv.selector == SEL_UNIFORM ? 1.0f / (float)sv.num_lights : select_pdf(sv, li, ps.o);
             float mis = sv.nee ? 1 / (1 + ps.inv_pdf * sel * pdf_s) : 1.0f;
             Lacc = add(Lacc, handle_color(sv, mulf(mul(ps.contrib, emit), mis)));
@@ -898,8 +949,9 @@ __device__ __forceinline__ int take_group(int* work, int& s, uint64_t& done, int
 }
 
 // path i of a generated chunk at its camera vertex (k_extend's fused bounce 0)
+template <bool FULL>
 __device__ __forceinline__ PathState camera_path(const FrameArgs& fa, const SceneView& sv, int i) {
-    const GenPath g = gen_path(fa, sv, i);
+    const GenPath g = gen_path<FULL>(fa, sv, i);
     PathState ps;
     ps.o = g.o;
     ps.d = g.d;
@@ -1026,7 +1078,7 @@ __global__ void __launch_bounds__(BT, LDS ? EXTEND_WAVES_LDS : (variant_full(V0)
         if (q < ns) {
             if (gen) { // inverse of gen_index
                 const int i = ((pos >> 6) << 12) | (s << 6) | (pos & 63);
-                ps = camera_path(fa, sv, i);
+                ps = camera_path<variant_full(V0)>(fa, sv, i);
                 if (variant_full(V0) && IGX_AOV && fa.aov_di) fa.aov_di[i] = fa.aov_nee[i] = make_float4(0, 0, 0, 0);
             } else {
                 ps = load_path(in, path_index(in, s, pos, sc));
@@ -1875,7 +1927,7 @@ __global__ void __launch_bounds__(BLOCK) k_infobuffer(FrameArgs fa, SceneView sv
         for (int k = 0; k < iters; ++k) {
             if (!info_pass_due(ia.mode, (int64_t)iter0 + k)) continue; // wave-uniform
             fa.iter = iter0 + k;
-            const GenPath g = gen_path(fa, sv, lp);
+            const GenPath g = gen_path<FULL>(fa, sv, lp);
             f3 o = g.o, d = g.d;
             Rng rnd{g.seed, g.counter};
             float tmin, tmax;
@@ -2136,6 +2188,9 @@ struct igx_device {
     std::vector<void*> scene_allocs;
     SceneView sv{};
     igx_camera cam_desc{};
+    // film size, frame and seed of igx_camera_rays: the scene's film until a
+    // render call (not in ray-list mode) sets its own
+    int rays_w = 0, rays_h = 0, rays_frame = 0, rays_seed = 0;
     int variant = 0;       // traversal variant of the scene (device_scene.h: width, spill)
     int bvh_width = 2;     // node width of the uploaded tables
     bool quantized = false; // the 4-wide nodes are quantised (Bvh4QNode, 64 B; variant bit 7)
@@ -2845,7 +2900,21 @@ IGX_TRACE_HELPERS(extern template, false)
 #endif
 #undef IGX_RES1
 
+// k_camera_rays (part 10) on dev->stream: `rays` takes 2 float4 per pixel of fa's film
+void launch_camera_rays(igx_device* dev, int grid, const FrameArgs& fa, const SceneView& sv, float4* rays);
+#if IGX_PART == 10
+void launch_camera_rays(igx_device* dev, int grid, const FrameArgs& fa, const SceneView& sv, float4* rays) {
+    hipLaunchKernelGGL(k_camera_rays, dim3(grid), dim3(BLOCK), 0, dev->stream, fa, sv, rays);
+}
+#endif
+
 #if IGX_PART == 0
+// k_generate on dev->stream, with the camera models of the scene's shading variant
+void launch_generate(igx_device* dev, int grid, const FrameArgs& fa, const PathBuf& out, float4* L, int* cnt0) {
+    if (dev->full_shading) hipLaunchKernelGGL(k_generate_full, dim3(grid), dim3(BLOCK), 0, dev->stream, fa, dev->sv, out, L, cnt0);
+    else hipLaunchKernelGGL(k_generate, dim3(grid), dim3(BLOCK), 0, dev->stream, fa, dev->sv, out, L, cnt0);
+}
+
 // Wait for the chunk last run in `s` and fold its statistics in.
 igx_status harvest(igx_device* dev, Slot& s) {
     if (!s.pending) return IGX_OK;
@@ -3011,31 +3080,8 @@ long long valid_pixels_in_chunk(const FrameArgs& fa) {
     return v;
 }
 
-DevCamera make_camera(const igx_device* dev, int width, int height) {
-    // make_perspective_camera (camera/perspective.art:29-42), compute_scale_from_{h,v}fov (:2-14)
-    const igx_camera& c = dev->cam_desc;
-    DevCamera k{};
-    float aspect = c.aspect > 0 ? c.aspect : (float)width / (float)height;
-    if (c.vertical_fov) {
-        k.scale_y = std::tan(c.fov / 2);
-        k.scale_x = k.scale_y * aspect;
-    } else {
-        k.scale_x = std::tan(c.fov / 2);
-        k.scale_y = k.scale_x / aspect;
-    }
-    float dir[3] = {c.dir[0], c.dir[1], c.dir[2]}, up[3] = {c.up[0], c.up[1], c.up[2]};
-    float r[3] = {dir[1] * up[2] - dir[2] * up[1], dir[2] * up[0] - dir[0] * up[2], dir[0] * up[1] - dir[1] * up[0]};
-    float rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-    float irl = 1 / rl;
-    for (int i = 0; i < 3; ++i) {
-        k.eye[i] = c.eye[i];
-        k.dir[i] = dir[i];
-        k.up[i] = up[i];
-        k.right[i] = r[i] * irl;
-    }
-    k.tmin = c.near_clip;
-    k.tmax = c.far_clip;
-    return k;
+CameraModel make_camera(const igx_device* dev, int width, int height) {
+    return make_camera_model(dev->cam_desc, width, height); // host/camera_model.h
 }
 
 #endif // IGX_PART == 0
@@ -3758,7 +3804,8 @@ extern "C" igx_status igx_upload_scene(igx_device* dev, const igx_scene_desc* de
     for (int pass = 0; pass < 2; ++pass)
         for (uint32_t l = 0; l < desc->num_lights; ++l) {
             const igx_light& L = desc->lights[l];
-            bool infinite = L.type == IGX_LIGHT_ENV || L.type == IGX_LIGHT_DIRECTIONAL || L.type == IGX_LIGHT_SUN;
+            bool infinite = L.type == IGX_LIGHT_ENV || L.type == IGX_LIGHT_DIRECTIONAL || L.type == IGX_LIGHT_SUN ||
+                            L.type == IGX_LIGHT_CIE; // a sky is infinite and not delta
             if ((pass == 0) != infinite) continue;
             DevLight d{};
             d.type = L.type;
@@ -3816,6 +3863,12 @@ extern "C" igx_status igx_upload_scene(igx_device* dev, const igx_scene_desc* de
                         return fail(dev, IGX_ERR_INVALID_ARGUMENT, "mesh light needs a non-empty triangle entity");
                     d.spot[0] = (float)desc->meshes[sh.mesh].num_faces;
                 }
+            } else if (L.type == IGX_LIGHT_CIE) {
+                if (L.sky_kind < IGX_SKY_UNIFORM || L.sky_kind > IGX_SKY_INTERMEDIATE)
+                    return fail(dev, IGX_ERR_INVALID_ARGUMENT, "invalid CIE sky kind");
+                static_assert(offsetof(DevLight, radiance) == 16 && sizeof(DevLight) == 16 + sizeof(CieSky), "CieSky lives behind the DevLight header");
+                const CieSky sky = make_cie_sky(L);
+                std::memcpy(d.radiance, &sky, sizeof(sky));
             } else if (L.type != IGX_LIGHT_ENV) {
                 return fail(dev, IGX_ERR_UNSUPPORTED, "unsupported light type");
             }
@@ -3960,6 +4013,9 @@ extern "C" igx_status igx_upload_scene(igx_device* dev, const igx_scene_desc* de
     sv.nee = desc->technique.nee;
     sv.clamp = desc->technique.clamp;
     dev->cam_desc = desc->camera;
+    dev->rays_w = desc->film_width;
+    dev->rays_h = desc->film_height;
+    dev->rays_frame = dev->rays_seed = 0;
     dev->aov_on = desc->technique.aov_mis != 0;
     dev->sv = sv;
     // stack: TLAS pushes + BLAS pushes (the depth for BVH2) + marker + resume entry + exit sentinel
@@ -3984,6 +4040,10 @@ extern "C" igx_status igx_upload_scene(igx_device* dev, const igx_scene_desc* de
         if (desc->lights[l].type == IGX_LIGHT_SPHERE || desc->lights[l].type == IGX_LIGHT_MESH) dev->full_shading = true;
     if (textured) dev->full_shading = true; // textures are looked up by the full shading variant only
     if (dev->aov_on) dev->full_shading = true; // so are the MIS AOVs (add_aov)
+    // and every camera but the pinhole perspective one (gen_pixel), and the CIE skies
+    if (camera_needs_full(desc->camera)) dev->full_shading = true;
+    for (uint32_t l = 0; l < desc->num_lights; ++l)
+        if (desc->lights[l].type == IGX_LIGHT_CIE) dev->full_shading = true;
     for (uint32_t e = 0; textured && e < desc->num_entities; ++e) {
         const igx_entity& en = desc->entities[e];
         if (desc->materials[en.material].texture != IGX_TEXTURE_NONE && desc->shapes[en.shape].type == IGX_SHAPE_SPHERE) {
@@ -4024,7 +4084,7 @@ extern "C" igx_status igx_upload_scene(igx_device* dev, const igx_scene_desc* de
 // has drained (wait_idle).
 struct ChunkPlan { // one render call's chunking (render_impl)
     FrameArgs fa{};
-    DevCamera cam{};
+    CameraModel cam{};
     int iteration = 0, spi = 1, count = 1, width = 1;
     long long local_pixels = 0, chunk_pixels_max = 0;
     int iters_per_chunk = 1;
@@ -4035,7 +4095,7 @@ struct ChunkPlan { // one render call's chunking (render_impl)
 // One info-buffer pass (k_infobuffer): the iterations of one render call
 struct InfoPass {
     FrameArgs fa{}; // spi 1, one chunk of every local pixel, chunk_iters = the call's iterations
-    DevCamera cam{};
+    CameraModel cam{};
     InfoArgs ia{};
     int grid = 1;
 };
@@ -4138,7 +4198,7 @@ static igx_status queue_clear(igx_device* dev, uint32_t mask, hipStream_t strm) 
 // Launch an info-buffer pass on `strm`, whose spill columns are `spill`.
 static igx_status queue_info_pass(igx_device* dev, const InfoPass& ps, hipStream_t strm, int* spill) {
     SceneView sv = dev->sv;
-    sv.cam = ps.cam;
+    set_camera(sv, ps.cam);
     sv.spill = spill;
     hipEvent_t a = nullptr, b = nullptr;
     if (dev->timing) {
@@ -4168,7 +4228,7 @@ igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
     auto use_slot = [&](const SchedItem& r) {
         dev->stream = dev->tail_stream = slot_stream[r.slot];
         dev->sv.spill = dev->spill_tail = slot_spill[r.slot];
-        dev->sv.cam = r.plan->cam;
+        set_camera(dev->sv, r.plan->cam);
     };
     auto restore = [&]() {
         dev->stream = main0;
@@ -4267,7 +4327,7 @@ igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
                 IGX_CC(hipMemsetAsync(S.ctr + (size_t)WORK_ROW0 * CROW, 0, (size_t)4 * pl.max_bounces * CROW * sizeof(int), dev->stream));
             if (!r.fuse_gen) {
                 begin_timed(S, 2, -1, dev->stream);
-                hipLaunchKernelGGL(k_generate, dim3(grid_for(dev, r.n, 8)), dim3(BLOCK), 0, dev->stream, r.fa, dev->sv, S.pa, S.L, S.ctr);
+                launch_generate(dev, grid_for(dev, r.n, 8), r.fa, S.pa, S.L, S.ctr);
                 end_timed(S, dev->stream);
                 IGX_CC(hipGetLastError());
             }
@@ -4616,8 +4676,14 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
         dev->fb_count = fbc;
         dev->iteration_count = 0;
     }
-    const DevCamera cam = make_camera(dev, width, height);
-    if (!async) dev->sv.cam = cam; // the worker sets each chunk's camera itself
+    if (!list_mode) {
+        dev->rays_w = width;
+        dev->rays_h = height;
+        dev->rays_frame = p->frame;
+        dev->rays_seed = p->seed;
+    }
+    const CameraModel cam = make_camera(dev, width, height);
+    if (!async) set_camera(dev->sv, cam); // the worker sets each chunk's camera itself
 
     FrameArgs fa{};
     fa.width = width;
@@ -4827,7 +4893,7 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
         const bool fuse_gen = dev->fuse_generate && !split && n > tail;
         if (!fuse_gen) {
             begin_timed(2, -1, dev->stream);
-            hipLaunchKernelGGL(k_generate, dim3(grid_for(dev, n, 8)), dim3(BLOCK), 0, dev->stream, fa, dev->sv, S.pa, S.L, cnt);
+            launch_generate(dev, grid_for(dev, n, 8), fa, S.pa, S.L, cnt);
             end_timed(dev->stream);
             HIPCHK(hipGetLastError());
         }
@@ -4945,8 +5011,45 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
 
 extern "C" igx_status igx_set_camera(igx_device* dev, const igx_camera* camera) {
     if (!dev || !camera) return IGX_ERR_INVALID_ARGUMENT;
+    // the basic shading variant compiles the pinhole perspective camera only
+    if (dev->has_scene && !dev->full_shading && camera_needs_full(*camera))
+        return fail(dev, IGX_ERR_UNSUPPORTED, "this camera needs the full shading variant: upload the scene with it, or with option full_shading");
     // queued chunks read the camera from their kernel arguments: no drain needed
     dev->cam_desc = *camera;
+    return IGX_OK;
+}
+
+extern "C" igx_status igx_camera_rays(igx_device* dev, int32_t iteration, int32_t sample, float* rays8, int32_t device_out) {
+    if (!dev || !rays8 || sample < 0) return IGX_ERR_INVALID_ARGUMENT;
+    if (!dev->has_scene) return fail(dev, IGX_ERR_NO_SCENE, "no scene uploaded");
+    const int w = dev->rays_w, h = dev->rays_h;
+    if (w < 1 || h < 1) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "no film size for camera rays");
+    // the kernel numbers (pixel, sample) as a path slot: pixel * (sample + 1) + sample
+    if ((long long)w * h * ((long long)sample + 1) > (1ll << 30)) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "film size times sample index too large for camera rays");
+    if (device_out && (reinterpret_cast<uintptr_t>(rays8) & 15)) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "device ray buffer must be 16-byte aligned");
+    HIPCHK(hipSetDevice(dev->hip_device));
+    igx_status st = drain(dev);
+    if (st != IGX_OK) return st;
+    const size_t bytes = (size_t)w * h * 8 * sizeof(float);
+    float4* d_rays = reinterpret_cast<float4*>(rays8);
+    if (!device_out) HIPCHK(hipMalloc((void**)&d_rays, bytes));
+    FrameArgs fa{};
+    fa.width = w;
+    fa.height = h;
+    fa.spi = sample + 1;
+    fa.chunk_pixels = w * h;
+    fa.chunk_iters = 1;
+    fa.iter = iteration;
+    fa.frame = dev->rays_frame;
+    fa.seed = dev->rays_seed;
+    SceneView sv = dev->sv;
+    set_camera(sv, make_camera(dev, w, h));
+    launch_camera_rays(dev, grid_for(dev, (long long)w * h, MAX_BLOCKS_PER_CU), fa, sv, d_rays);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
+    if (e == hipSuccess && !device_out) e = hipMemcpy(rays8, d_rays, bytes, hipMemcpyDeviceToHost);
+    if (!device_out) (void)hipFree(d_rays);
+    HIPCHK(e);
     return IGX_OK;
 }
 

@@ -8,6 +8,9 @@
 
 #include "device_math.h"
 #include "device_scene.h"
+#include "../host/cie_sky.h"
+
+#include <cstddef>
 
 namespace igxd {
 
@@ -30,12 +33,19 @@ struct SceneView {
     int max_depth, min_depth, nee;
     float clamp;
     int num_nodes, num_inst, num_tris; // table sizes (for staging the traversal tables in LDS)
+    // The camera model and lens (host/camera_model.h DevLens), read by the full
+    // shading variant only.  The three words sit in what were the struct's
+    // alignment holes, so every other field keeps its offset and the basic
+    // variant's kernels their code.
+    int cam_type;          // IGX_CAMERA_*
     // treelet: nodes [0, tree_n) of `nodes` (the hottest, igx_upload_scene's
     // hot order) staged in LDS at `tree` by stage_treelet (variant_tree kernels)
     const float4* tree;
     int tree_n;
+    float cam_aperture;    // depth of field: lens radius
     int* spill;            // traversal-stack overflow area of the launching stream (see TStack)
     int node_f4;           // float4s per BVH node (4: BVH2, 8: 4-wide)
+    float cam_focal;       // depth of field: distance of the plane in focus
     const int* ent_enc;    // per entity: its index among the enclosing entities (trace_enclosed), else -1
     const int2* enc;       // per enclosing entity: entity id, TLAS leaf slot
     const float4* enc_box; // per enclosing entity: world box lo.xyz, hi.xyz (path classes, option path_classes 3)
@@ -60,6 +70,16 @@ struct SceneView {
     // records, fsh face records, fn_tab entries, materials
     int num_ent, num_fsh, num_fn, num_mats;
 };
+
+static_assert(sizeof(SceneView) == 320 && offsetof(SceneView, cam_type) == 188 && offsetof(SceneView, cam_aperture) == 204 &&
+                  offsetof(SceneView, cam_focal) == 220,
+              "the camera model fills SceneView's alignment holes");
+__host__ __device__ inline void set_camera(SceneView& sv, const CameraModel& m) {
+    sv.cam = m.cam;
+    sv.cam_type = m.lens.type;
+    sv.cam_aperture = m.lens.aperture_radius;
+    sv.cam_focal = m.lens.focal_length;
+}
 
 // Copy the traversal tables (nodes, instances, triangles) of a small scene
 // into LDS, laid out back to back, and point a block-local view at them: the
@@ -1128,6 +1148,30 @@ __device__ __forceinline__ float pdf_as_solid(float value, bool solid, float cos
     return solid ? value : value * dist2 / cos; // driver/pdf.art:15-32
 }
 
+// ---- CIE skies (LIGHT_CIE, host/cie_sky.h; full shading variant only) ----
+// make_environment_light_function (light/env.art:25-108): with a ground the
+// sky covers the sphere and is sampled uniformly, without one it covers the
+// upper hemisphere of its Y-up frame and is cosine-sampled.
+__device__ __forceinline__ const CieSky& cie_sky_of(const DevLight& L) { return *reinterpret_cast<const CieSky*>(L.radiance); }
+// Light::emission and pdf_direct (solid angle) for the ray direction `rd`
+// leaving the scene (env.art:48-60, 88-89)
+__device__ __forceinline__ void cie_emission(const DevLight& L, f3 rd, f3& emit, float& pdf_s) {
+    const CieSky& sky = cie_sky_of(L);
+    const SkyVec local = cie_to_local(sky, SkyVec{rd.x, rd.y, rd.z});
+    if (cie_has_ground(sky)) {
+        const SkyVec e = cie_sky_radiance(sky, local);
+        emit = mk(e.x, e.y, e.z);
+        pdf_s = 1 / (4 * PI_);
+    } else if (local.y > FLT_EPS_) {
+        const SkyVec e = cie_sky_radiance(sky, local);
+        emit = mk(e.x, e.y, e.z);
+        pdf_s = local.y / PI_; // cosine_hemisphere_pdf (core/sampling.art:62)
+    } else {
+        emit = mk(0, 0, 0);
+        pdf_s = 0;
+    }
+}
+
 // Light::sample_direct for the light types on the hot path
 template <bool FULL>
 __device__ __forceinline__ DirectSample light_sample_direct(const SceneView& sv, const DevLight& L, Rng& rnd,
@@ -1171,6 +1215,34 @@ __device__ __forceinline__ DirectSample light_sample_direct(const SceneView& sv,
         f3 dir = equal_area_square_to_sphere(ux, uy);
         float pdf = 1 / (4 * PI_);
         ds.intensity = mulf(rad, 1 / pdf);
+        ds.pos = add(from.point, mulf(dir, sv.scene_radius));
+        ds.dir = dir;
+        ds.pdf_value = pdf;
+        ds.pdf_solid = true;
+        ds.cos = 1.0f;
+        ds.dist = sv.scene_radius;
+    } else if (FULL && L.type == LIGHT_CIE) {
+        const CieSky& sky = cie_sky_of(L);
+        float ux = rnd.next_f32();
+        float uy = rnd.next_f32();
+        SkyVec e;
+        f3 dir;
+        float pdf;
+        if (cie_has_ground(sky)) {
+            // ..._spherical.sample_direct (env.art:80-84): uniform over the sphere
+            dir = equal_area_square_to_sphere(ux, uy);
+            pdf = 1 / (4 * PI_);
+            e = cie_sky_radiance(sky, cie_to_local(sky, SkyVec{dir.x, dir.y, dir.z}));
+        } else {
+            // ..._hemi.sample_direct (env.art:31-36): cosine-weighted about the sky's
+            // +Y (switch_env_up), taken to world space by mat3x3_left_mul
+            const f3 sd = sample_cosine_hemisphere(ux, uy, &pdf);
+            const SkyVec local{sd.x, sd.z, sd.y};
+            e = cie_sky_radiance(sky, local);
+            const SkyVec g = cie_to_world(sky, local);
+            dir = mk(g.x, g.y, g.z);
+        }
+        ds.intensity = mulf(mk(e.x, e.y, e.z), 1 / pdf);
         ds.pos = add(from.point, mulf(dir, sv.scene_radius));
         ds.dir = dir;
         ds.pdf_value = pdf;

@@ -18,8 +18,9 @@
 //     reaches the device through igx_set_camera;
 //   * render's ParameterSet (RuntimeStructs.h:56-70) carries the runtime's
 //     camera orientation (__camera_eye / __camera_dir / __camera_up,
-//     Runtime::setCameraOrientationParameter, Runtime.cpp:700-705), which
-//     overrides the shading view's camera; its other parameters drive the
+//     Runtime::setCameraOrientationParameter, Runtime.cpp:700-705) and the
+//     orthogonal camera's __camera_scale (OrthogonalCamera.cpp:30), which
+//     override the shading view's camera; its other parameters drive the
 //     reference's shading networks, which igx does not have, and are ignored;
 //   * capture_shading builds the shader set of an in-memory scene
 //     (igx_objscene_*, the `const Scene*` of Runtime::loadFromScene) without a
@@ -273,6 +274,8 @@ public:
             put("__camera_eye", cam.eye);
             put("__camera_dir", cam.dir);
             put("__camera_up", cam.up);
+            // the orthogonal camera's scale (OrthogonalCamera.cpp:30)
+            if (auto it = params->FloatParameters.find("__camera_scale"); it != params->FloatParameters.end()) cam.ortho_scale = it->second;
         }
         if (std::memcmp(&cam, &mCamera, sizeof(cam)) != 0) {
             check(igx_set_camera(mDev, &cam));

@@ -12,7 +12,10 @@
 #include "linalg.h"
 #include "mesh.h"
 #include "scene_store.h"
+#include "cie_sky.h"
+#include "sun_position.h"
 
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -286,6 +289,42 @@ M4 get_transform(const Props& p, const char* key = "transform") {
     t.at(3, 0) = t.at(3, 1) = t.at(3, 2) = 0;
     t.at(3, 3) = 1;
     return t;
+}
+
+// LoaderUtils::getEA (LoaderUtils.cpp:140-151): the sun of a directional, sun
+// or CIE sky light from a direction, from elevation / azimuth or from date,
+// time and place (computeSunEA with the reference's defaults)
+igx::ElevationAzimuth get_ea(const Props& lp) {
+    if (lp.has("direction") || lp.has("sun_direction")) {
+        V3 d = igx::normalized(lp.vec3(lp.has("direction") ? "direction" : "sun_direction", V3(0, 0, 1)));
+        float theta = std::acos(d.y), phi = std::atan2(d.x, -d.z); // ElevationAzimuth::fromDirectionYUp
+        return {1.57079632679f - theta, phi < 0 ? phi + 6.28318530718f : phi};
+    }
+    if (lp.has("elevation") || lp.has("azimuth")) return {lp.number("elevation", 0.0f), lp.number("azimuth", 0.0f)};
+    igx::SunTime t;
+    igx::SunPlace p;
+    t.year = (int)lp.integer("year", t.year);
+    t.month = (int)lp.integer("month", t.month);
+    t.day = (int)lp.integer("day", t.day);
+    t.hour = (int)lp.integer("hour", t.hour);
+    t.minute = (int)lp.integer("minute", t.minute);
+    t.seconds = lp.number("seconds", t.seconds);
+    p.latitude = lp.number("latitude", p.latitude);
+    p.longitude = lp.number("longitude", p.longitude);
+    p.timezone = lp.number("timezone", p.timezone);
+    return igx::compute_sun_ea(t, p);
+}
+// ElevationAzimuth::toDirectionYUp (ElevationAzimuth.h:23-31)
+V3 ea_direction(igx::ElevationAzimuth ea) {
+    return V3(std::cos(ea.elevation) * std::sin(ea.azimuth), std::sin(ea.elevation), -std::cos(ea.elevation) * std::cos(ea.azimuth));
+}
+// IGX_SKY_* of a CIE sky's type name (LoaderLight.cpp:90-97), -1 for any other light
+int cie_sky_kind(const std::string& type) {
+    if (type == "cie_uniform" || type == "cieuniform") return IGX_SKY_UNIFORM;
+    if (type == "cie_cloudy" || type == "ciecloudy") return IGX_SKY_CLOUDY;
+    if (type == "cie_clear" || type == "cieclear") return IGX_SKY_CLEAR;
+    if (type == "cie_intermediate" || type == "cieintermediate") return IGX_SKY_INTERMEDIATE;
+    return -1;
 }
 
 // Scene-level merge of externals, as the reference parser does it:
@@ -892,24 +931,47 @@ static void build_scene(SceneStore& S, const Value& doc, const std::string& base
             } else if (type == "directional" || type == "sun") {
                 // DirectionalLight.cpp:20-32, SunLight.cpp:24-46; direction via
                 // LoaderUtils::getEA(...).toDirectionYUp() (LoaderUtils.cpp:140-156)
-                V3 dir;
-                if (lp.has("direction") || lp.has("sun_direction")) {
-                    V3 d = igx::normalized(lp.vec3(lp.has("direction") ? "direction" : "sun_direction", V3(0, 0, 1)));
-                    float theta = std::acos(d.y), phi = std::atan2(d.x, -d.z); // ElevationAzimuth::fromDirectionYUp
-                    float el = 1.57079632679f - theta, az = phi < 0 ? phi + 6.28318530718f : phi;
-                    dir = V3(std::cos(el) * std::sin(az), std::sin(el), -std::cos(el) * std::cos(az));
-                } else if (lp.has("elevation") || lp.has("azimuth")) {
-                    float el = lp.number("elevation", 0.0f), az = lp.number("azimuth", 0.0f);
-                    dir = V3(std::cos(el) * std::sin(az), std::sin(el), -std::cos(el) * std::cos(az));
-                } else {
-                    fail("light '" + name + "': give 'direction', 'sun_direction' or 'elevation'/'azimuth' (time/location sun positions are not supported)");
-                }
+                const V3 dir = ea_direction(get_ea(lp));
                 V3 E = lp.color("irradiance", V3(1, 1, 1));
                 L.type = type == "sun" ? IGX_LIGHT_SUN : IGX_LIGHT_DIRECTIONAL;
                 for (int i = 0; i < 3; ++i) { L.normal[i] = dir[i]; L.radiance[i] = E[i]; }
                 if (type == "sun")
                     L.cutoff = lp.has("radius") ? 1 / std::sqrt(lp.number("radius", 1.0f) * lp.number("radius", 1.0f) + 1) // sun_cos_angle_from_radius
                                                 : std::cos(lp.number("angle", 11.4f) * kDeg2Rad / 2);
+            } else if (cie_sky_kind(type) >= 0) {
+                // CIELight.cpp:9-110.  Constant colours only (Props::color); they reach
+                // the reference's shader as registry parameters, i.e. unrounded
+                L.type = IGX_LIGHT_CIE;
+                L.sky_kind = cie_sky_kind(type);
+                L.has_ground = lp.boolean("has_ground", true) ? 1 : 0;
+                const V3 zenith = lp.color("zenith", V3(1, 1, 1)), ground = lp.color("ground", V3(1, 1, 1));
+                const V3 scale = lp.color("scale", V3(1, 1, 1));
+                L.ground_brightness = lp.number("ground_brightness", 0.2f);
+                igx::ElevationAzimuth ea = get_ea(lp);
+                // mSunDirection is taken before the elevation clamp (CIELight.cpp:14, 66-69);
+                // inlineVector prints it at stream precision
+                const V3 sun = ea_direction(ea);
+                for (int i = 0; i < 3; ++i) {
+                    L.sky_zenith[i] = zenith[i];
+                    L.sky_ground[i] = ground[i];
+                    L.sky_scale[i] = scale[i];
+                    L.sun_direction[i] = igxd::cie_printed(sun[i]);
+                }
+                if (L.sky_kind == IGX_SKY_CLEAR || L.sky_kind == IGX_SKY_INTERMEDIATE) {
+                    ea.elevation = std::min(ea.elevation, 87 * kDeg2Rad);
+                    igxd::cie_sunny_constants(L.sky_kind == IGX_SKY_CLEAR, ea.elevation, sun.y, lp.number("turbidity", 2.45f),
+                                              L.zenith_ratio, L.sky_c2);
+                }
+                // transform.linear().transpose().inverse(); inlineMatrix writes an identity
+                // as such and prints any other matrix at stream precision
+                const igx::M3 tm = igx::inverse3(igx::transpose3(igx::linear_of(get_transform(lp))));
+                bool identity = true;
+                for (int i = 0; i < 9; ++i) identity = identity && std::abs(tm.m[i] - (i % 4 == 0 ? 1.0f : 0.0f)) <= 1e-5f; // Eigen isIdentity
+                for (int i = 0; i < 9; ++i) L.sky_transform[i] = identity ? (i % 4 == 0 ? 1.0f : 0.0f) : igxd::cie_printed(tm.m[i]);
+                // CIELight::computeFlux (CIELight.cpp:17-24): zenith * pi * r^2 (half without ground)
+                const V3 diam = scene_bbox.empty() ? V3() : scene_bbox.diameter();
+                const float radius = igx::norm(diam) / 2;
+                L.select_flux = (zenith.x + zenith.y + zenith.z) / 3 * kPi * radius * radius * (L.has_ground ? 1.0f : 0.5f);
             } else {
                 fail("light '" + name + "': unsupported light type '" + type + "'");
             }
@@ -956,8 +1018,23 @@ static void build_scene(SceneStore& S, const Value& doc, const std::string& base
     const Value* camv = doc.find("camera");
     Props cp{camv};
     if (camv) {
+        // LoaderCamera.cpp:27-38: perspective, orthogonal, fishlens / fisheye
         std::string type = cp.string("type", "perspective");
-        if (type != "perspective") fail("unsupported camera type '" + type + "'");
+        for (char& ch : type) ch = (char)std::tolower((unsigned char)ch);
+        if (type == "perspective") cam.type = IGX_CAMERA_PERSPECTIVE;
+        else if (type == "orthogonal") cam.type = IGX_CAMERA_ORTHOGONAL;
+        else if (type == "fishlens" || type == "fisheye") cam.type = IGX_CAMERA_FISHLENS;
+        else fail("unsupported camera type '" + type + "'");
+        if (cam.type == IGX_CAMERA_ORTHOGONAL) cam.ortho_scale = cp.number("scale", 1.0f); // OrthogonalCamera.cpp:18
+        if (cam.type == IGX_CAMERA_PERSPECTIVE) {
+            // PerspectiveCamera.cpp:21-22, 55-75: the lens is printed into the shader at stream
+            // precision; focal_length matters with an aperture only
+            const float aperture = cp.number("aperture_radius", 0.0f);
+            if (aperture > 1.1920928955e-07f) {
+                cam.aperture_radius = igxd::cie_printed(aperture);
+                cam.focal_length = igxd::cie_printed(cp.number("focal_length", 1.0f));
+            }
+        }
         if (cp.has("vfov")) { cam.vertical_fov = 1; cam.fov = cp.number("vfov", 60) * kDeg2Rad; }
         else if (cp.has("hfov")) cam.fov = cp.number("hfov", 60) * kDeg2Rad;
         else cam.fov = cp.number("fov", 60) * kDeg2Rad;
@@ -965,9 +1042,10 @@ static void build_scene(SceneStore& S, const Value& doc, const std::string& base
         cam.near_clip = cp.number("near_clip", 0.0f);
         cam.far_clip = cp.number("far_clip", 3.4028234664e+38f);
         if (cam.far_clip < cam.near_clip) std::swap(cam.near_clip, cam.far_clip);
-        if (cp.number("aperture_radius", 0.0f) > 1.1920928955e-07f) fail("depth-of-field camera is not supported");
     }
-    if (camv && cp.has("transform")) {
+    // the orthogonal and fishlens cameras take their orientation from the transform
+    // alone, an identity without one (OrthogonalCamera.cpp:58-66, FishLensCamera.cpp:61-69)
+    if (camv && (cp.has("transform") || cam.type != IGX_CAMERA_PERSPECTIVE)) {
         M4 t = get_transform(cp);
         V3 eye = igx::xform_point(t, V3());
         for (int i = 0; i < 3; ++i) { cam.eye[i] = eye[i]; cam.dir[i] = t.at(i, 2); cam.up[i] = t.at(i, 1); }

@@ -282,6 +282,7 @@ class Device:
             raise IgxError(f"igx_create({hip_device}) failed with status {st}")
         self._h = h
         self._film = None  # (width, height) of the last render: the shape of tonemap()
+        self._rays_film = None  # (width, height) of camera_rays(): the scene's film, then the last render's
 
     def _check(self, st):
         if st != 0:
@@ -292,9 +293,13 @@ class Device:
 
     def upload(self, scene):
         self._check(self._lib.igx_upload_scene(self._h, scene.desc_ptr))
+        d = scene.desc
+        self._rays_film = (d.film_width, d.film_height)
 
     def _rendered(self, params):
         self._film = (params.num_rays, 1) if params.num_rays > 0 else (params.width, params.height)
+        if params.num_rays <= 0:
+            self._rays_film = (params.width, params.height)
 
     def render(self, params):
         self._check(self._lib.igx_render(self._h, C.byref(params)))
@@ -431,6 +436,20 @@ class Device:
                                              ep.ctypes.data_as(C.POINTER(C.c_int32)),
                                              tuv.ctypes.data_as(C.POINTER(C.c_float))))
         return ep, tuv
+
+    def camera_rays(self, iteration=0, sample=0):
+        """The camera rays the renderer traces for sample `sample` of iteration
+        `iteration` (igx_camera_rays): an (height, width, 8) array of org, dir,
+        tmin, tmax, for the film, frame and seed of the last render call (the
+        uploaded scene's film, frame 0 and seed 0 before the first) and the
+        current camera.  Feed it to trace_hits or to ray-list mode."""
+        if self._rays_film is None:
+            raise IgxError("camera_rays: no scene uploaded")
+        w, h = self._rays_film
+        out = np.zeros((h, w, 8), dtype=np.float32)
+        self._check(self._lib.igx_camera_rays(self._h, int(iteration), int(sample),
+                                              out.ctypes.data_as(C.POINTER(C.c_float)), 0))
+        return out
 
     def trace_occlusion(self, rays, flags=0x8):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)

@@ -48,6 +48,11 @@ class Material(C.Structure):
 
 # igx_light.type (include/igx_scene.h)
 LIGHT_PLANE, LIGHT_ENV, LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL, LIGHT_SUN, LIGHT_SPHERE, LIGHT_MESH = range(1, 9)
+LIGHT_CIE = 9
+# igx_light.sky_kind
+SKY_UNIFORM, SKY_CLOUDY, SKY_CLEAR, SKY_INTERMEDIATE = range(4)
+# igx_camera.type
+CAMERA_PERSPECTIVE, CAMERA_ORTHOGONAL, CAMERA_FISHLENS = range(3)
 
 
 class Light(C.Structure):
@@ -55,12 +60,18 @@ class Light(C.Structure):
                 ("origin", C.c_float * 3), ("x_axis", C.c_float * 3), ("y_axis", C.c_float * 3),
                 ("normal", C.c_float * 3), ("area", C.c_float), ("cutoff", C.c_float), ("falloff", C.c_float),
                 ("radius", C.c_float), ("select_position", C.c_float * 3), ("select_direction", C.c_float * 3),
-                ("select_has_direction", C.c_int32), ("select_flux", C.c_float)]
+                ("select_has_direction", C.c_int32), ("select_flux", C.c_float),
+                ("sky_kind", C.c_int32), ("has_ground", C.c_int32), ("sky_zenith", C.c_float * 3),
+                ("sky_ground", C.c_float * 3), ("sky_scale", C.c_float * 3), ("ground_brightness", C.c_float),
+                ("sun_direction", C.c_float * 3), ("zenith_ratio", C.c_float), ("sky_c2", C.c_float),
+                ("sky_transform", C.c_float * 9)]
 
 
 class Camera(C.Structure):
     _fields_ = [("eye", C.c_float * 3), ("dir", C.c_float * 3), ("up", C.c_float * 3), ("fov", C.c_float),
-                ("vertical_fov", C.c_int32), ("aspect", C.c_float), ("near_clip", C.c_float), ("far_clip", C.c_float)]
+                ("vertical_fov", C.c_int32), ("aspect", C.c_float), ("near_clip", C.c_float), ("far_clip", C.c_float),
+                ("type", C.c_int32), ("ortho_scale", C.c_float), ("aperture_radius", C.c_float),
+                ("focal_length", C.c_float)]
 
 
 class Technique(C.Structure):
@@ -170,7 +181,7 @@ EXPORTED_SYMBOLS = [
     "igx_render", "igx_get_framebuffer", "igx_framebuffer_device_ptr", "igx_get_aov", "igx_aov_device_ptr",
     "igx_pack_tiles", "igx_clear", "igx_get_stats", "igx_reset_stats", "igx_trace_hits", "igx_trace_occlusion", "igx_synchronize", "igx_wait_ready",
     "igx_render_iterations", "igx_objscene_create", "igx_objscene_free", "igx_objscene_add",
-    "igx_objscene_set_property", "igx_scene_from_objects", "igx_set_camera",
+    "igx_objscene_set_property", "igx_scene_from_objects", "igx_set_camera", "igx_camera_rays",
     "igx_clear_aov", "igx_aov_iteration_count", "igx_write_exr_layers",
     "igx_tonemap", "igx_imageinfo", "igx_tonemap_film", "igx_imageinfo_film",
 ]
@@ -212,6 +223,7 @@ def lib():
     L.igx_scene_from_objects.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.igx_scene_from_objects.restype = vp
     L.igx_set_camera.argtypes = [vp, C.POINTER(Camera)]
+    L.igx_camera_rays.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32]
     L.igx_write_exr.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_float]
     L.igx_write_exr.restype = C.c_int
     L.igx_write_exr_layers.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_float)), C.c_int32,
@@ -251,7 +263,8 @@ def lib():
     for name in ["igx_create", "igx_destroy", "igx_set_option", "igx_upload_scene", "igx_render", "igx_render_iterations",
                  "igx_get_framebuffer", "igx_framebuffer_device_ptr", "igx_get_aov", "igx_aov_device_ptr",
                  "igx_pack_tiles", "igx_clear", "igx_clear_aov", "igx_aov_iteration_count",
-                 "igx_synchronize", "igx_wait_ready", "igx_get_stats", "igx_reset_stats", "igx_trace_hits", "igx_trace_occlusion"]:
+                 "igx_synchronize", "igx_wait_ready", "igx_get_stats", "igx_reset_stats", "igx_trace_hits", "igx_trace_occlusion",
+                 "igx_set_camera", "igx_camera_rays"]:
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

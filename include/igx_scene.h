@@ -124,8 +124,11 @@ enum {
     IGX_LIGHT_DIRECTIONAL = 5, /* light/directional.art:1-19 */
     IGX_LIGHT_SUN   = 6, /* light/sun.art:4-30 (delta, infinite) */
     IGX_LIGHT_SPHERE = 7, /* area light on a (near-)spherical entity: make_sphere_area_emitter (light/area.art:240-293) */
-    IGX_LIGHT_MESH  = 8  /* area light on any triangle entity: make_shape_area_emitter (light/area.art:45-105) */
+    IGX_LIGHT_MESH  = 8, /* area light on any triangle entity: make_shape_area_emitter (light/area.art:45-105) */
+    IGX_LIGHT_CIE   = 9  /* analytic CIE sky: make_cie_sky_light / make_cie_sunny_light (light/cie.art:9-42) */
 };
+/* igx_light.sky_kind (CIELight.h CIEType; LoaderLight.cpp:90-97) */
+enum { IGX_SKY_UNIFORM = 0, IGX_SKY_CLOUDY = 1, IGX_SKY_CLEAR = 2, IGX_SKY_INTERMEDIATE = 3 };
 
 typedef struct igx_light {
     int32_t type;
@@ -145,15 +148,38 @@ typedef struct igx_light {
     float select_direction[3];
     int32_t select_has_direction;
     float select_flux;     /* mean of the light's power colour */
+    /* IGX_LIGHT_CIE (CIELight.cpp:42-110); zero for every other type.  The sky
+     * is Y-up in its own frame: L(d) is evaluated at sky_transform * d
+     * (has_ground: the whole sphere, sampled uniformly; otherwise the upper
+     * hemisphere only, cosine-sampled, light/env.art:25-108) */
+    int32_t sky_kind;      /* IGX_SKY_* */
+    int32_t has_ground;
+    float sky_zenith[3], sky_ground[3], sky_scale[3]; /* scale: clear / intermediate only */
+    float ground_brightness;
+    float sun_direction[3];/* towards the sun, Y-up (ElevationAzimuth::toDirectionYUp) */
+    float zenith_ratio;    /* zenith brightness / factor (clear / intermediate) */
+    float sky_c2;          /* ground term of the clear / intermediate sky */
+    float sky_transform[9];/* transform.linear().transpose().inverse(), row-major */
 } igx_light;
 
 /* ---- camera / technique ------------------------------------------------ */
+enum {
+    IGX_CAMERA_PERSPECTIVE = 0, /* camera/perspective.art:29-42; with aperture_radius > FLT_EPSILON the
+                                   depth-of-field camera (:74-120) */
+    IGX_CAMERA_ORTHOGONAL  = 1, /* camera/orthogonal.art:14-46 */
+    IGX_CAMERA_FISHLENS    = 2  /* camera/fishlens.art:8-68, circular aspect mode (FishLensCamera.cpp:9) */
+};
 typedef struct igx_camera {
     float eye[3], dir[3], up[3];
     float fov;             /* radians */
     int32_t vertical_fov;  /* 1: fov is vertical (compute_scale_from_vfov) */
     float aspect;          /* <= 0: use film width / height */
     float near_clip, far_clip;
+    /* the fields below are zero for the pinhole perspective camera */
+    int32_t type;          /* IGX_CAMERA_* */
+    float ortho_scale;     /* orthogonal: half width of the view in world units (scale; height = scale / aspect) */
+    float aperture_radius; /* perspective: lens radius, > FLT_EPSILON selects depth of field */
+    float focal_length;    /* perspective with depth of field: distance of the plane in focus */
 } igx_camera;
 
 /* light selection for next-event estimation (LoaderLight::generateLightSelector,

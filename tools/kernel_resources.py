@@ -1,4 +1,4 @@
-"""Dev tool: per-kernel VGPR / spill / LDS usage of the gfx950 code object in
+"""Dev tool: per-kernel VGPR / SGPR / spill / scratch / LDS usage of the gfx950 code object in
 build/igx_device_p*.o (reads the AMDGPU metadata notes).
 usage: kernel_resources.py [name filter] [objects...]"""
 import glob
@@ -21,4 +21,5 @@ for b in notes.split(".name:")[1:]:
         continue
     dn = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
     g = lambda k: (re.search(r"\." + k + r":\s+(\d+)", b) or [None, "-"])[1]
-    print(f"{dn[:70]:70s} vgpr {g('vgpr_count'):>4} spill {g('vgpr_spill_count'):>3} priv {g('private_segment_fixed_size'):>4} lds {g('group_segment_fixed_size'):>6}")
+    print(f"{dn[:70]:70s} vgpr {g('vgpr_count'):>4} spill {g('vgpr_spill_count'):>3} sgpr {g('sgpr_count'):>4} sspill {g('sgpr_spill_count'):>3} "
+          f"priv {g('private_segment_fixed_size'):>4} lds {g('group_segment_fixed_size'):>6}")
