@@ -1,12 +1,20 @@
-// Device-resident scene and stream layouts (shared by host upload code and kernels).
+// Device-resident scene and stream layouts (shared by the host's table builder,
+// host/scene_tables.cpp, the upload code and the kernels; compiles without HIP).
 // See DESIGN.md "HBM layout".  All arrays are 16-byte element aligned so every
 // record is fetched with global_load_dwordx4.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifndef __HIPCC__
 struct float4_ { float x, y, z, w; };
+#endif
+
+#ifdef __HIPCC__
+#define IGX_SCENE_HD __host__ __device__
+#else
+#define IGX_SCENE_HD
 #endif
 
 namespace igxd {
@@ -21,27 +29,28 @@ constexpr int LEAF_COUNT_BITS = 4;
 // the scene's stack need exceeds the LDS stack, so pushes and pops check for
 // the spill area; bit 2 = the scene uses materials or lights beyond the basic
 // set (igx_kernels.h, bsdf_eval), compiled into the shading kernels only then.
-// The upload picks the variant per scene.
+// build_scene_tables (host/scene_tables.cpp) picks the variant per scene.
 #ifndef IGX_LDS_STACK
 #define IGX_LDS_STACK 16
 #endif
 constexpr int LDS_STACK = IGX_LDS_STACK; // LDS traversal-stack entries per lane
-__host__ __device__ constexpr int variant_width(int v) { return (v & 2) ? 4 : 2; }
-__host__ __device__ constexpr bool variant_spill(int v) { return (v & 1) != 0; }
-__host__ __device__ constexpr bool variant_full(int v) { return (v & 4) != 0; }
-__host__ __device__ constexpr int node_f4(int width) { return width == 4 ? 8 : 4; }
+constexpr int MAX_STACK = 128;           // traversal stack entries (LDS + spill) per ray
+IGX_SCENE_HD constexpr int variant_width(int v) { return (v & 2) ? 4 : 2; }
+IGX_SCENE_HD constexpr bool variant_spill(int v) { return (v & 1) != 0; }
+IGX_SCENE_HD constexpr bool variant_full(int v) { return (v & 4) != 0; }
+IGX_SCENE_HD constexpr int node_f4(int width) { return width == 4 ? 8 : 4; }
 // Bit 3: the node tables are staged in LDS (stage_scene_lds; set by the
 // kernels on their LDS-staged SceneView).  The node steps then skip the
 // stack-top peek (IGX_PEEK_POP), whose extra LDS read costs there what it
 // saves where the nodes come from global memory.  (One float4 of padding per
 // LDS node, round 2, measured neutral and was removed.)
-__host__ __device__ constexpr bool variant_lds_nodes(int v) { return (v & 8) != 0; }
+IGX_SCENE_HD constexpr bool variant_lds_nodes(int v) { return (v & 8) != 0; }
 // Bit 4: if-if stepping (trav_step advances one inner node or one leaf per
 // call) -- set only on k_shadow_refill launches for scenes on the split
 // schedule (igx_device.hip, use_shadow_ifif).
-__host__ __device__ constexpr bool variant_ifif(int v) { return (v & 16) != 0; }
+IGX_SCENE_HD constexpr bool variant_ifif(int v) { return (v & 16) != 0; }
 // Bit 5: the node tables stay in global memory, but the hottest nodes (the
-// first SceneView::tree_n of the node array, igx_upload_scene's hot order)
+// first SceneView::tree_n of the node array, order_hot_nodes' hot order)
 // are staged in LDS (the treelet); node steps below that index read LDS.
 // Set by every kernel instantiation that does not stage the whole table.
 constexpr int VARIANT_TREE = 32;
@@ -50,10 +59,10 @@ constexpr int VARIANT_TREE = 32;
 // tables stay in global memory.  Set by the upload with bit 1 (option
 // "bvh_quantize").
 constexpr int VARIANT_Q4 = 128;
-__host__ __device__ constexpr bool variant_q4(int v) { return (v & VARIANT_Q4) != 0; }
+IGX_SCENE_HD constexpr bool variant_q4(int v) { return (v & VARIANT_Q4) != 0; }
 constexpr int32_t REF_EMPTY = (int32_t)0x80000002; // absent child of a 4-wide node (host kEmptyRef)
-__host__ __device__ constexpr bool variant_tree(int v) { return (v & VARIANT_TREE) != 0; }
-__host__ __device__ constexpr int kernel_variant(int v, bool lds) { return lds ? (v | 8) : (v | VARIANT_TREE); }
+IGX_SCENE_HD constexpr bool variant_tree(int v) { return (v & VARIANT_TREE) != 0; }
+IGX_SCENE_HD constexpr int kernel_variant(int v, bool lds) { return lds ? (v | 8) : (v | VARIANT_TREE); }
 
 // Instance record (one per TLAS leaf slot): 64 B
 //   row0..row2: to_local 3x4 (row-major, xyz = linear row, w = translation)
@@ -61,6 +70,14 @@ __host__ __device__ constexpr int kernel_variant(int v, bool lds) { return lds ?
 //         index (trimesh) or sphere index (sphere), w = visibility flags
 // The reference's EntityLeaf1 (traversal/bvh.art:52-61) carries the same data
 // plus the entity box, which here lives in the parent TLAS node.
+// Flag in info.w, next to the visibility bits: the trimesh instance's to_local
+// is the identity, so its entity-space ray is the world ray (instance_test
+// skips the transform; set by build_scene_tables)
+constexpr uint32_t INST_IDENTITY = 1u << 30;
+// ... or a pure translation (rows (1 0 0 tx), (0 1 0 ty), (0 0 1 tz)): the
+// entity-space ray is (o + t, d), so its reciprocal direction is the world
+// ray's (IGX_TRANSLATE_INSTANCES)
+constexpr uint32_t INST_TRANSLATE = 1u << 29;
 
 // Per-entity shading record: 3 rows of to_global, 3 rows of normal matrix,
 // info (shape, material, vtx_offset, idx_offset) -> 7 x 16 B.
@@ -97,6 +114,31 @@ struct DevLight {      // 128 B
                        // sphere: emitter area (compute_ellipsoid_area); mesh: face count
     float pad2[4];
 };
+
+// Enclosing entities (trace_enclosed): a path's slot word carries 1 + the
+// index of the enclosing entity it is in in its top 5 bits, so at most 31 of
+// them; their world boxes are staged in LDS (stage_enc_boxes)
+constexpr int MAX_ENCLOSING = 31;
+constexpr int MAX_ENC_BOXES = 32;
+static_assert(MAX_ENCLOSING <= MAX_ENC_BOXES, "enclosing boxes are staged in LDS (stage_enc_boxes)");
+
+// Limits and thresholds of the table build (host/scene_tables.cpp).
+// BLAS with more triangles build without spatial splits (load time; their
+// triangles are small next to the scene in the suite's soups)
+constexpr uint32_t SPATIAL_SPLIT_MAX_FACES = 1u << 21;
+// face instances (faces x entities using them) up to which the upload
+// precomputes world-space face normals (16 B each: at most 64 MB)
+constexpr size_t FACE_NORMAL_TABLE_MAX = 4u << 20;
+// mesh faces (over all shapes) up to which the upload writes the per-face
+// shading records SceneView::fsh (48 B each: at most 192 MB)
+constexpr size_t FACE_SHADE_MAX = 4u << 20;
+// nodes moved to the front of the node array in hot order at upload (the
+// largest treelet a kernel may stage: 160 KB of LDS / 128-B nodes)
+constexpr size_t TREELET_FRONT = 1280;
+// traversal tables beyond this go to the split schedule (use_split in
+// igx_device.hip, "Kernel schedule per scene"), and 4-wide nodes of scenes
+// estimated beyond it are quantised (build_scene_tables)
+constexpr size_t SPLIT_TABLE_BYTES = 64u << 20;
 
 } // namespace igxd
 

@@ -27,8 +27,7 @@
 #include "device_math.h"
 #include "device_scene.h"
 #include "igx_kernels.h"
-#include "../host/bvh_build.h"
-#include "../host/light_select.h"
+#include "../host/scene_tables.h"
 #include "../host/lds_plan.h"
 #include "../host/extend_shape.h"
 #include "../host/aov_plan.h"
@@ -37,7 +36,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <chrono>
 #include <map>
 #include <cmath>
@@ -80,14 +78,12 @@ constexpr int BLOCK = 256;
 constexpr int BLOCK_WIDE = LDS_PLAN_BLOCK_WIDE;
 static_assert(BLOCK == LDS_PLAN_BLOCK, "host/lds_plan.h plans for BLOCK-thread blocks");
 [[maybe_unused]] constexpr int MAX_BLOCKS_PER_CU = 8;  // 2048 threads per CU; grids never exceed num_cus * this
-[[maybe_unused]] constexpr int MAX_STACK = 128;        // traversal stack entries (LDS + spill) per ray
 constexpr int MAX_BOUNCES = 256;          // path depth is stored in 8 bits (p1.w, above the 24-bit RNG counter)
 constexpr long long MAX_CHUNK_PATHS = 1ll << 27; // paths per chunk (one wavefront), ~25 GB of stream buffers per slot
 // a path's slot in its chunk takes the low 27 bits of the slot word; the top
-// 5 carry 1 + the index of the enclosing entity it is in (at most 31 entities)
+// 5 carry 1 + the index of the enclosing entity it is in (at most MAX_ENCLOSING)
 constexpr int SLOT_BITS = 27;
 constexpr uint32_t SLOT_MASK = (1u << SLOT_BITS) - 1;
-[[maybe_unused]] constexpr int MAX_ENCLOSING = 31;
 static_assert(MAX_CHUNK_PATHS <= (1ll << SLOT_BITS), "path slots must fit the slot bits");
 // Occupancy target (waves per SIMD) of k_extend, with global and with
 // LDS-staged traversal tables: 4 caps it at 128 VGPRs.  k_finish keeps the
@@ -2043,19 +2039,7 @@ constexpr int WORK_ROW0 = 2 * MAX_BOUNCES + 4;
 // shading sub-phase clocks by class, 70-71 k_shadow rays by class
 [[maybe_unused]] constexpr int DSTATS = 80;
 constexpr int CTR_ROWS = WORK_ROW0 + 4 * MAX_BOUNCES;
-// BLAS with more triangles build without spatial splits (load time; their
-// triangles are small next to the scene in the suite's soups)
-[[maybe_unused]] constexpr uint32_t SPATIAL_SPLIT_MAX_FACES = 1u << 21;
-// face instances (faces x entities using them) up to which the upload
-// precomputes world-space face normals (16 B each: at most 64 MB)
-[[maybe_unused]] constexpr size_t FACE_NORMAL_TABLE_MAX = 4u << 20;
-// mesh faces (over all shapes) up to which the upload writes the per-face
-// shading records SceneView::fsh (48 B each: at most 192 MB)
-[[maybe_unused]] constexpr size_t FACE_SHADE_MAX = 4u << 20;
 [[maybe_unused]] constexpr size_t CTR_INTS = (size_t)CTR_ROWS * CROW;
-// nodes moved to the front of the node array in hot order at upload (the
-// largest treelet a kernel may stage: 160 KB of LDS / 128-B nodes)
-[[maybe_unused]] constexpr size_t TREELET_FRONT = 1280;
 
 // records in counter row `row` of the slot's host mirror (row 0: generated paths)
 inline long long row_total(const Slot& s, int row) {
@@ -2285,14 +2269,21 @@ igx_status fail(igx_device* d, igx_status s, const std::string& msg) {
                         std::string(#expr) + ": " + hipGetErrorString(e_));                           \
     } while (0)
 
-template <typename T>
-igx_status upload(igx_device* dev, const std::vector<T>& v, const T** out) {
+// Copy a host table to the device.  T is the table's host element type
+// (host/scene_tables.h), D the type the kernels read it as.
+static_assert(sizeof(igx::Float4) == sizeof(float4) && alignof(igx::Float4) == alignof(float4), "igx::Float4 is the device's float4");
+static_assert(sizeof(igx::Int4) == sizeof(int4) && alignof(igx::Int4) == alignof(int4), "igx::Int4 is the device's int4");
+static_assert(sizeof(igx::Float2) == sizeof(float2) && alignof(igx::Float2) == alignof(float2), "igx::Float2 is the device's float2");
+static_assert(sizeof(igx::Int2) == sizeof(int2) && alignof(igx::Int2) == alignof(int2), "igx::Int2 is the device's int2");
+template <typename T, typename D>
+igx_status upload(igx_device* dev, const std::vector<T>& v, const D** out) {
+    static_assert(sizeof(T) == sizeof(D) && alignof(T) == alignof(D), "the host element is the device element");
     size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
     void* p = nullptr;
     HIPCHK(hipMalloc(&p, bytes));
     dev->scene_allocs.push_back(p);
     if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = reinterpret_cast<const T*>(p);
+    *out = reinterpret_cast<const D*>(p);
     return IGX_OK;
 }
 
@@ -2428,7 +2419,6 @@ int grid_for(igx_device* dev, long long items, int blocks_per_cu, int block = BL
 //    and lets lanes refill.  Below, the fused kernel with dynamic groups is
 //    faster (no hit records): S-deep (18 MB of tables) 49.4 -> 46.9 ms per
 //    8-iteration frame fused, soup-1M (104 MB) 382 split vs 451 fused.
-constexpr size_t SPLIT_TABLE_BYTES = 64u << 20;
 // order in which k_extend's dynamic groups take a shard's positions (option "group_order" -1)
 #ifndef GROUP_ORDER_AUTO
 #define GROUP_ORDER_AUTO 0
@@ -3312,745 +3302,90 @@ extern "C" igx_status igx_synchronize(igx_device* dev) {
     return drain(dev);
 }
 
-// A closed triangle mesh: with vertices welded by position, every edge
-// borders exactly two faces (paths that enter it by transmission then hit it
-// again before leaving).  Checked up to 1 M faces.
-// Hot order of the node array for the LDS treelet (stage_treelet): the
-// `front` inner nodes a ray most likely visits move to indices [0, front), so
-// a kernel stages any prefix of the array as its treelet.  Visit likelihood
-// follows the surface-area heuristic: the TLAS root has 1; a child has its
-// parent's times the child box's area over the union of the sibling boxes
-// (the chance a ray through the parent also crosses the child); a BLAS root
-// collects the likelihood of every TLAS leaf that instances it.  The other
-// nodes keep their relative (depth-first) order.  Every inner-node reference
-// (node children, instance BLAS roots, the TLAS root) is renumbered; the
-// traversal result does not depend on node numbering.
-// `format`: 2 (BVH2, 64 B), 4 (4-wide, 128 B) or 5 (quantised 4-wide, 64 B).
-static void order_hot_nodes(std::vector<float4>& nodes, int format, std::vector<float4>& inst, int& tlas_root, size_t front) {
-    const int nf4 = format == 4 ? 8 : 4;
-    const size_t nn = nodes.size() / nf4;
-    if (nn == 0 || front == 0) return;
-    const int width = format == 2 ? 2 : 4;
-    auto ref = [&](size_t n, int k) -> int32_t& {
-        return reinterpret_cast<int32_t*>(&nodes[n * nf4])[format == 4 ? 24 + k : 12 + k];
-    };
-    auto box = [&](size_t n, int k, float lo[3], float hi[3]) {
-        const float* f = reinterpret_cast<const float*>(&nodes[n * nf4]);
-        if (format == 5) { // origin + code * scale (Bvh4QNode)
-            const uint32_t* u = reinterpret_cast<const uint32_t*>(f);
-            const float sc[3] = {f[3], f[4], f[5]};
-            for (int a = 0; a < 3; ++a) {
-                lo[a] = f[a] + (float)((u[6 + 2 * a] >> (8 * k)) & 255u) * sc[a];
-                hi[a] = f[a] + (float)((u[7 + 2 * a] >> (8 * k)) & 255u) * sc[a];
-            }
-            if (ref(n, k) == igx::kEmptyRef) lo[0] = INFINITY;
-            return;
-        }
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = width == 4 ? f[8 * a + k] : f[6 * k + 2 * a];
-            hi[a] = width == 4 ? f[8 * a + 4 + k] : f[6 * k + 2 * a + 1];
-        }
-    };
-    auto half_area = [](const float lo[3], const float hi[3]) -> double {
-        for (int a = 0; a < 3; ++a)
-            if (!std::isfinite(lo[a]) || !std::isfinite(hi[a]) || lo[a] > hi[a]) return 0.0;
-        const double dx = (double)hi[0] - lo[0], dy = (double)hi[1] - lo[1], dz = (double)hi[2] - lo[2];
-        return dx * dy + dy * dz + dz * dx;
-    };
-    // children of node n with the node's likelihood pn: f(child ref, child likelihood)
-    auto children = [&](size_t n, double pn, auto&& f) {
-        float ulo[3] = {INFINITY, INFINITY, INFINITY}, uhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        double ak[4] = {0, 0, 0, 0};
-        for (int k = 0; k < width; ++k) {
-            float lo[3], hi[3];
-            box(n, k, lo, hi);
-            ak[k] = half_area(lo, hi);
-            if (ak[k] <= 0) continue;
-            for (int a = 0; a < 3; ++a) {
-                ulo[a] = std::min(ulo[a], lo[a]);
-                uhi[a] = std::max(uhi[a], hi[a]);
-            }
-        }
-        const double ua = half_area(ulo, uhi);
-        for (int k = 0; k < width; ++k) {
-            const int32_t r = ref(n, k);
-            if (r == igx::kEmptyRef || ak[k] <= 0) continue;
-            f(r, ua > 0 ? pn * std::min(1.0, ak[k] / ua) : pn);
-        }
-    };
-    std::vector<double> p(nn, 0.0), pblas(nn, 0.0);
-    auto instances = [&](int32_t leaf, double pl) { // TLAS leaf: its instances' BLAS roots
-        const int code = ~leaf;
-        const int first = code >> igx::kLeafCountBits, count = (code & ((1 << igx::kLeafCountBits) - 1)) + 1;
-        for (int k = 0; k < count; ++k) {
-            int4 info;
-            std::memcpy(&info, &inst[4 * (size_t)(first + k) + 3], 16);
-            if (info.y == 0 && info.z >= 0 && (size_t)info.z < nn) pblas[info.z] += pl;
-        }
-    };
-    std::vector<std::pair<int32_t, double>> todo;
-    if (tlas_root >= 0) todo.push_back({tlas_root, 1.0});
-    else if (!inst.empty()) instances(tlas_root, 1.0); // one entity: the root is its leaf
-    while (!todo.empty()) { // TLAS (a tree)
-        const auto [n, pn] = todo.back();
-        todo.pop_back();
-        p[n] += pn;
-        children((size_t)n, pn, [&](int32_t r, double pc) {
-            if (r >= 0) todo.push_back({r, pc});
-            else instances(r, pc);
-        });
-    }
-    for (size_t r = 0; r < nn; ++r) { // every BLAS from its root (a BLAS is a tree; shared BLAS summed at the root)
-        if (pblas[r] <= 0) continue;
-        todo.push_back({(int32_t)r, pblas[r]});
-        while (!todo.empty()) {
-            const auto [n, pn] = todo.back();
-            todo.pop_back();
-            p[n] += pn;
-            children((size_t)n, pn, [&](int32_t c, double pc) {
-                if (c >= 0) todo.push_back({c, pc});
-            });
-        }
-    }
-    std::vector<int32_t> order(nn);
-    for (size_t i = 0; i < nn; ++i) order[i] = (int32_t)i;
-    front = std::min(front, nn);
-    std::partial_sort(order.begin(), order.begin() + front, order.end(), [&](int32_t a, int32_t b) {
-        return p[a] != p[b] ? p[a] > p[b] : a < b;
-    });
-    std::vector<int32_t> newidx(nn, -1);
-    for (size_t i = 0; i < front; ++i) newidx[order[i]] = (int32_t)i;
-    int32_t next = (int32_t)front;
-    for (size_t i = 0; i < nn; ++i)
-        if (newidx[i] < 0) newidx[i] = next++;
-    std::vector<float4> out(nodes.size());
-    for (size_t i = 0; i < nn; ++i) std::copy(&nodes[i * nf4], &nodes[i * nf4] + nf4, &out[(size_t)newidx[i] * nf4]);
-    nodes.swap(out);
-    for (size_t i = 0; i < nn; ++i)
-        for (int k = 0; k < width; ++k)
-            if (ref(i, k) >= 0) ref(i, k) = newidx[ref(i, k)];
-    for (size_t slot = 0; slot < inst.size() / 4; ++slot) {
-        int4 info;
-        std::memcpy(&info, &inst[4 * slot + 3], 16);
-        if (info.y == 0 && info.z >= 0) {
-            info.z = newidx[info.z];
-            std::memcpy(&inst[4 * slot + 3], &info, 16);
-        }
-    }
-    if (tlas_root >= 0) tlas_root = newidx[tlas_root];
-}
-
-static bool closed_mesh(const igx_mesh& m) {
-    if (m.num_faces < 4 || m.num_faces > (1u << 20)) return false;
-    std::map<std::array<float, 3>, uint32_t> weld;
-    std::vector<uint32_t> id(m.num_vertices);
-    for (uint32_t v = 0; v < m.num_vertices; ++v)
-        id[v] = weld.emplace(std::array<float, 3>{m.vertices[3 * v], m.vertices[3 * v + 1], m.vertices[3 * v + 2]}, (uint32_t)weld.size()).first->second;
-    std::map<std::pair<uint32_t, uint32_t>, int> edges;
-    for (uint32_t f = 0; f < m.num_faces; ++f)
-        for (int k = 0; k < 3; ++k) {
-            uint32_t a = id[m.indices[3 * f + k]], b = id[m.indices[3 * f + (k + 1) % 3]];
-            if (a == b) return false;
-            ++edges[{std::min(a, b), std::max(a, b)}];
-        }
-    for (const auto& e : edges)
-        if (e.second != 2) return false;
-    return true;
-}
-
+// The scene tables are built on the host (host/scene_tables.cpp, which also
+// validates the description and picks node width, quantisation and shading
+// variant); this copies them to the device and configures the handle.
 extern "C" igx_status igx_upload_scene(igx_device* dev, const igx_scene_desc* desc) {
     if (!dev || !desc) return IGX_ERR_INVALID_ARGUMENT;
     HIPCHK(hipSetDevice(dev->hip_device));
     reset_async_failure(dev); // a new scene starts the handle afresh
-    igx_status dst = drain(dev);
-    if (dst != IGX_OK) return dst;
+    igx_status st = drain(dev);
+    if (st != IGX_OK) return st;
     free_scene(dev);
 
-    // ---- phase 1: BVH2 of every trimesh shape and of the entity TLAS ------
-    std::vector<igx::BvhBuildResult> brs(desc->num_shapes);
-    int blas_depth2 = 0;
-    for (uint32_t s = 0; s < desc->num_shapes; ++s) {
-        const igx_shape& sh = desc->shapes[s];
-        if (sh.type == IGX_SHAPE_SPHERE) continue;
-        if (sh.mesh < 0 || (uint32_t)sh.mesh >= desc->num_meshes)
-            return fail(dev, IGX_ERR_INVALID_ARGUMENT, "shape references an invalid mesh");
-        const igx_mesh& m = desc->meshes[sh.mesh];
-        igx::BvhBuildInput bi;
-        bi.bmin.resize(3 * m.num_faces);
-        bi.bmax.resize(3 * m.num_faces);
-        bi.centroid.resize(3 * m.num_faces);
-        for (uint32_t f = 0; f < m.num_faces; ++f) {
-            for (int a = 0; a < 3; ++a) {
-                float lo = 3.4e38f, hi = -3.4e38f;
-                for (int k = 0; k < 3; ++k) {
-                    uint32_t vi = m.indices[3 * f + k];
-                    if (vi >= m.num_vertices) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "mesh index out of range");
-                    float v = m.vertices[3 * vi + a];
-                    lo = std::min(lo, v);
-                    hi = std::max(hi, v);
-                }
-                bi.bmin[3 * f + a] = lo;
-                bi.bmax[3 * f + a] = hi;
-                bi.centroid[3 * f + a] = 0.5f * (lo + hi);
-            }
-        }
-        if (sh.ref_bvh && !dev->rebuild_bvh) {
-            // the reference loader's BLAS (Node2 + Tri1, TriMeshProvider.cpp:553-554)
-            std::string err;
-            if (!igx::bvh2_from_reference(sh.ref_bvh, sh.ref_bvh_bytes, m.num_faces, brs[s], err))
-                return fail(dev, IGX_ERR_INVALID_ARGUMENT, "shape " + std::to_string(s) + ": " + err);
-            blas_depth2 = std::max(blas_depth2, brs[s].depth);
-            continue;
-        }
-        try {
-            if (dev->spatial_splits && m.num_faces <= SPATIAL_SPLIT_MAX_FACES) {
-                std::vector<float> tv(9 * (size_t)m.num_faces);
-                for (uint32_t f = 0; f < m.num_faces; ++f)
-                    for (int k = 0; k < 3; ++k)
-                        for (int a = 0; a < 3; ++a) tv[9 * (size_t)f + 3 * k + a] = m.vertices[3 * m.indices[3 * f + k] + a];
-                brs[s] = igx::build_sbvh2(bi, tv, dev->leaf_size);
-            } else {
-                brs[s] = igx::build_bvh2(bi, dev->leaf_size, dev->bvh_bins, dev->sah_node_cost);
-            }
-        } catch (const std::exception& ex) {
-            return fail(dev, IGX_ERR_INVALID_ARGUMENT, ex.what());
-        }
-        blas_depth2 = std::max(blas_depth2, brs[s].depth);
-    }
-    igx::BvhBuildResult tlas_br;
-    if (desc->num_entities > 0) {
-        igx::BvhBuildInput bi;
-        for (uint32_t e = 0; e < desc->num_entities; ++e) {
-            const igx_entity& en = desc->entities[e];
-            if (en.shape < 0 || (uint32_t)en.shape >= desc->num_shapes)
-                return fail(dev, IGX_ERR_INVALID_ARGUMENT, "entity references an invalid shape");
-            if (en.material < 0 || (uint32_t)en.material >= desc->num_materials)
-                return fail(dev, IGX_ERR_INVALID_ARGUMENT, "entity references an invalid material");
-            for (int a = 0; a < 3; ++a) {
-                bi.bmin.push_back(en.bbox_min[a]);
-                bi.bmax.push_back(en.bbox_max[a]);
-                bi.centroid.push_back(0.5f * (en.bbox_min[a] + en.bbox_max[a]));
-            }
-        }
-        tlas_br = igx::build_bvh2(bi, 1, dev->bvh_bins_tlas);
-    }
-    // Node width: BVH2 while its whole stack fits the LDS column (fewer,
-    // cheaper node steps on small scenes), else 4-wide nodes (half the node
-    // iterations on deep trees; the deepest entries spill).  Option
-    // "bvh_width" forces either.
-    const int width = dev->bvh_width_opt == 2 || dev->bvh_width_opt == 4
-                          ? dev->bvh_width_opt
-                          : (tlas_br.depth + blas_depth2 + 3 <= LDS_STACK ? 2 : 4);
-    // 4-wide nodes quantised to 64 B (Bvh4QNode) on the split schedule's
-    // scenes, whose node fetches go to the Infinity Cache / HBM (soup-16M frame
-    // 74.7 -> 70.0, soup-1M 98.2 -> 92.8 ms); where the tables stay on chip the
-    // decode only costs instructions (primitives 8.6 -> 9.4, S-deep 46.7 -> 49.5)
-    size_t est_tri = 0;
-    for (const auto& b : brs) est_tri += b.prim_order.size();
-    const size_t est_bytes = est_tri * 48 + (size_t)desc->num_entities * 64 + (est_tri / 2 + desc->num_entities) * 128;
-    const bool quantize = width == 4 && (dev->quantize_opt == 1 || (dev->quantize_opt < 0 && est_bytes > SPLIT_TABLE_BYTES));
-    const int nf4 = quantize ? 4 : node_f4(width);
+    igx::SceneBuildOptions opt;
+    opt.rebuild_bvh = dev->rebuild_bvh;
+    opt.spatial_splits = dev->spatial_splits;
+    opt.leaf_size = dev->leaf_size;
+    opt.bvh_bins = dev->bvh_bins;
+    opt.bvh_bins_tlas = dev->bvh_bins_tlas;
+    opt.sah_node_cost = dev->sah_node_cost;
+    opt.bvh_width_opt = dev->bvh_width_opt;
+    opt.quantize_opt = dev->quantize_opt;
+    opt.face_shade_opt = dev->face_shade_opt != 0;
+    opt.face_normals_opt = dev->face_normals_opt != 0;
+    opt.enclosing_opt = dev->enclosing_opt;
+    opt.full_shading_opt = dev->full_shading_opt;
+    igx::SceneTables t;
+    std::string error;
+    if ((st = igx::build_scene_tables(*desc, opt, t, error)) != IGX_OK) return fail(dev, st, error);
 
-    // ---- phase 2: node, triangle and instance tables ----------------------
-    std::vector<float4> nodes; // nf4 float4s per node
-    std::vector<float4> tris, vtx, nrm, spheres;
-    std::vector<float2> uvs; // texture coordinates, only for scenes with a textured material
-    bool textured = false;
-    for (uint32_t i = 0; i < desc->num_materials; ++i) textured = textured || desc->materials[i].texture != IGX_TEXTURE_NONE;
-    std::vector<int4> idx;
-    // per face: vertex normals and indices in one record (SceneView::fsh),
-    // for scenes with at most FACE_SHADE_MAX faces over all meshes (48 B each)
-    std::vector<float4> fsh;
-    size_t total_faces = 0;
-    for (uint32_t i = 0; i < desc->num_shapes; ++i)
-        if (desc->shapes[i].type != IGX_SHAPE_SPHERE && desc->shapes[i].mesh >= 0) total_faces += desc->meshes[desc->shapes[i].mesh].num_faces;
-    const bool with_fsh = dev->face_shade_opt && total_faces <= FACE_SHADE_MAX;
-    // Append a built BVH2 (as Node2, or collapsed to 4-wide nodes) to the
-    // unified node array: inner refs move by the array offset, leaf codes by
-    // `leaf_off` slots.  Returns the node offset; `need` = stack entries the
-    // tree can occupy.
-    auto append_nodes = [&](const igx::BvhBuildResult& br, int leaf_off, int& need) -> int {
-        const int node_off = (int)(nodes.size() / nf4);
-        auto move_leaf = [&](int32_t ref) {
-            int code = ~ref;
-            return igx::encode_leaf((code >> igx::kLeafCountBits) + leaf_off, (code & ((1 << igx::kLeafCountBits) - 1)) + 1);
-        };
-        if (width == 2) {
-            for (auto nd : br.nodes) {
-                for (int k = 0; k < 2; ++k) {
-                    if (nd.ref[k] >= 0) nd.ref[k] += node_off;
-                    else if (nd.ref[k] != igx::kEmptyRef && nd.b[k * 6] <= nd.b[k * 6 + 1])
-                        nd.ref[k] = move_leaf(nd.ref[k]); // empty and absent children keep their code
-                }
-                float4 f[4];
-                std::memcpy(f, &nd, 64);
-                nodes.insert(nodes.end(), f, f + 4);
-            }
-            need = br.depth;
-        } else {
-            igx::Bvh4Result b4 = igx::collapse_bvh4(br);
-            for (auto nd : b4.nodes) {
-                for (int k = 0; k < 4; ++k) {
-                    if (nd.ref[k] >= 0) nd.ref[k] += node_off;
-                    else if (nd.ref[k] != igx::kEmptyRef) nd.ref[k] = move_leaf(nd.ref[k]);
-                }
-                if (quantize) {
-                    const igx::Bvh4QNode qn = igx::quantize_bvh4(nd);
-                    float4 f[4];
-                    std::memcpy(f, &qn, 64);
-                    nodes.insert(nodes.end(), f, f + 4);
-                } else {
-                    float4 f[8];
-                    std::memcpy(f, &nd, 128);
-                    nodes.insert(nodes.end(), f, f + 8);
-                }
-            }
-            need = b4.stack_need;
-        }
-        return node_off;
-    };
-    struct ShapeDev { int type, root, vtx_off, idx_off_or_sphere; };
-    std::vector<ShapeDev> sdev(desc->num_shapes);
-    int blas_depth = 0;
-    for (uint32_t s = 0; s < desc->num_shapes; ++s) {
-        const igx_shape& sh = desc->shapes[s];
-        if (sh.type == IGX_SHAPE_SPHERE) {
-            sdev[s] = {1, -1, 0, (int)spheres.size()};
-            spheres.push_back(make_float4(sh.sphere[0], sh.sphere[1], sh.sphere[2], sh.sphere[3]));
-            continue;
-        }
-        const igx_mesh& m = desc->meshes[sh.mesh];
-        const igx::BvhBuildResult& br = brs[s];
-        int tri_off = (int)(tris.size() / 3);
-        if (tri_off + br.prim_order.size() >= (size_t)(1 << 26))
-            return fail(dev, IGX_ERR_UNSUPPORTED, "too many triangles for the leaf encoding");
-        int need = 0;
-        int node_off = append_nodes(br, tri_off, need);
-        blas_depth = std::max(blas_depth, need);
-        for (uint32_t slot = 0; slot < br.prim_order.size(); ++slot) {
-            uint32_t f = br.prim_order[slot];
-            const uint32_t* ix = m.indices + 3 * f;
-            const float* v0 = m.vertices + 3 * ix[0];
-            const float* v1 = m.vertices + 3 * ix[1];
-            const float* v2 = m.vertices + 3 * ix[2];
-            // Tri1 (shapes/trimesh.art:107-114; TriBVHAdapter.h:148-158): e1 = v0 - v1, e2 = v2 - v0
-            float4 q0 = make_float4(v0[0], v0[1], v0[2], 0);
-            int32_t pid = (int32_t)f;
-            std::memcpy(&q0.w, &pid, 4);
-            tris.push_back(q0);
-            tris.push_back(make_float4(v0[0] - v1[0], v0[1] - v1[1], v0[2] - v1[2], 0));
-            tris.push_back(make_float4(v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2], 0));
-        }
-        // a BLAS that is a single leaf is entered at the leaf itself
-        int root_ref = node_off;
-        if (br.root_is_leaf) {
-            int code = ~br.root_leaf_ref;
-            root_ref = igx::encode_leaf((code >> igx::kLeafCountBits) + tri_off, (code & ((1 << igx::kLeafCountBits) - 1)) + 1);
-        }
-        sdev[s] = {0, root_ref, (int)vtx.size(), (int)idx.size()};
-        for (uint32_t v = 0; v < m.num_vertices; ++v) {
-            vtx.push_back(make_float4(m.vertices[3 * v], m.vertices[3 * v + 1], m.vertices[3 * v + 2], 0));
-            nrm.push_back(make_float4(m.normals[3 * v], m.normals[3 * v + 1], m.normals[3 * v + 2], 0));
-            if (textured) uvs.push_back(m.texcoords ? make_float2(m.texcoords[2 * v], m.texcoords[2 * v + 1]) : make_float2(0, 0));
-        }
-        for (uint32_t f = 0; f < m.num_faces; ++f)
-            idx.push_back(make_int4((int)m.indices[3 * f], (int)m.indices[3 * f + 1], (int)m.indices[3 * f + 2], 0));
-        if (with_fsh)
-            for (uint32_t f = 0; f < m.num_faces; ++f)
-                for (int k = 0; k < 3; ++k) {
-                    const uint32_t v = m.indices[3 * f + k];
-                    float4 r = make_float4(m.normals[3 * v], m.normals[3 * v + 1], m.normals[3 * v + 2], 0);
-                    const int vi = (int)v;
-                    std::memcpy(&r.w, &vi, 4);
-                    fsh.push_back(r);
-                }
-        brs[s] = igx::BvhBuildResult{}; // release the host copy
-    }
-
-    // ---- TLAS over entities (leaf size 1), instance records ---------------
-    std::vector<float4> inst, ent;
-    std::vector<int> ent_fn;       // per entity: first face-normal entry, -1 without a table
-    std::vector<float4> fn_tab;    // world-space unit face normals (surface_element)
-    std::vector<int> ent_enc; // per entity: enclosing index or -1
-    std::vector<int2> enc_tab; // per enclosing index: entity, TLAS leaf slot
-    std::vector<float4> enc_box; // per enclosing index: world box lo, hi
-    int tlas_root = -1;
-    int tlas_depth = 0;
-    if (desc->num_entities > 0) {
-        const igx::BvhBuildResult& br = tlas_br;
-        int node_off = append_nodes(br, 0, tlas_depth);
-        tlas_root = br.root_is_leaf ? br.root_leaf_ref : node_off; // single entity: start at its leaf
-        for (uint32_t slot = 0; slot < br.prim_order.size(); ++slot) {
-            uint32_t e = br.prim_order[slot];
-            const igx_entity& en = desc->entities[e];
-            const ShapeDev& sd = sdev[en.shape];
-            for (int r = 0; r < 3; ++r)
-                inst.push_back(make_float4(en.to_local[r * 4 + 0], en.to_local[r * 4 + 1], en.to_local[r * 4 + 2], en.to_local[r * 4 + 3]));
-            static const float kIdentity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-            const float* m = en.to_local;
-            const bool linear_identity = m[0] == 1 && m[1] == 0 && m[2] == 0 && m[4] == 0 && m[5] == 1 && m[6] == 0 &&
-                                         m[8] == 0 && m[9] == 0 && m[10] == 1 && std::isfinite(m[3]) &&
-                                         std::isfinite(m[7]) && std::isfinite(m[11]);
-            const bool identity = sd.type == 0 && std::equal(m, m + 12, kIdentity);
-            const bool translate = sd.type == 0 && !identity && linear_identity;
-            const uint32_t iflags = (en.flags & ~(INST_IDENTITY | INST_TRANSLATE)) | (identity ? INST_IDENTITY : 0u) |
-                                    (translate ? INST_TRANSLATE : 0u);
-            int4 info = make_int4((int)e, sd.type, sd.type == 1 ? sd.idx_off_or_sphere : sd.root, (int)iflags);
-            float4 fi;
-            std::memcpy(&fi, &info, 16);
-            inst.push_back(fi);
-        }
-        // enclosing entities (trace_enclosed): a closed mesh of a non-thin
-        // dielectric whose world box keeps a margin from every other entity's
-        // box, at most MAX_ENCLOSING of them (ent_enc: index, enc_tab: entity and TLAS leaf slot)
-        ent_enc.assign(desc->num_entities, -1);
-        if (dev->enclosing_opt && desc->num_entities <= 4096) {
-            float slo[3], shi[3];
-            for (int a = 0; a < 3; ++a) { slo[a] = desc->scene_bbox_min[a]; shi[a] = desc->scene_bbox_max[a]; }
-            const float margin = 1e-4f * std::max({shi[0] - slo[0], shi[1] - slo[1], shi[2] - slo[2], 1e-6f});
-            std::vector<int> closed(desc->num_shapes, -1);
-            for (uint32_t slot = 0; slot < br.prim_order.size(); ++slot) {
-                const uint32_t e = br.prim_order[slot];
-                const igx_entity& en = desc->entities[e];
-                const igx_shape& sh = desc->shapes[en.shape];
-                const igx_material& mat = desc->materials[en.material];
-                if (sh.type != IGX_SHAPE_TRIMESH || mat.bsdf_type != IGX_BSDF_DIELECTRIC || mat.thin) continue;
-                if (closed[en.shape] < 0) closed[en.shape] = closed_mesh(desc->meshes[sh.mesh]) ? 1 : 0;
-                if (!closed[en.shape]) continue;
-                bool apart = true;
-                for (uint32_t o = 0; o < desc->num_entities && apart; ++o) {
-                    if (o == e) continue;
-                    const igx_entity& q = desc->entities[o];
-                    bool overlap = true;
-                    for (int a = 0; a < 3; ++a)
-                        overlap = overlap && q.bbox_min[a] <= en.bbox_max[a] + margin && en.bbox_min[a] <= q.bbox_max[a] + margin;
-                    apart = !overlap;
-                }
-                static_assert(MAX_ENCLOSING <= MAX_ENC_BOXES, "enclosing boxes are staged in LDS (stage_enc_boxes)");
-                if (apart && (int)enc_tab.size() < MAX_ENCLOSING) {
-                    ent_enc[e] = (int)enc_tab.size();
-                    enc_tab.push_back(make_int2((int)e, (int)slot));
-                    enc_box.push_back(make_float4(en.bbox_min[0], en.bbox_min[1], en.bbox_min[2], 0));
-                    enc_box.push_back(make_float4(en.bbox_max[0], en.bbox_max[1], en.bbox_max[2], 0));
-                }
-            }
-        }
-        for (uint32_t e = 0; e < desc->num_entities; ++e) {
-            const igx_entity& en = desc->entities[e];
-            const ShapeDev& sd = sdev[en.shape];
-            for (int r = 0; r < 3; ++r)
-                ent.push_back(make_float4(en.to_global[r * 4 + 0], en.to_global[r * 4 + 1], en.to_global[r * 4 + 2], en.to_global[r * 4 + 3]));
-            for (int r = 0; r < 3; ++r) ent.push_back(make_float4(en.normal[r * 3 + 0], en.normal[r * 3 + 1], en.normal[r * 3 + 2], 0));
-            int4 info = make_int4(sd.type, en.material, sd.vtx_off, sd.idx_off_or_sphere);
-            float4 fi;
-            std::memcpy(&fi, &info, 16);
-            ent.push_back(fi);
-        }
-        // world-space unit face normals of every (mesh entity, face) when the
-        // scene has few face instances: surface_element then skips three vertex
-        // loads and transforms per hit.  make_triangle (core/triangle.art:11-26)
-        // on the entity's to_global rows, in float, same operation order.
-        size_t face_instances = 0;
-        for (uint32_t e = 0; e < desc->num_entities; ++e) {
-            const igx_shape& sh = desc->shapes[desc->entities[e].shape];
-            if (sh.type == IGX_SHAPE_TRIMESH && sh.mesh >= 0) face_instances += desc->meshes[sh.mesh].num_faces;
-        }
-        if (dev->face_normals_opt && face_instances > 0 && face_instances <= FACE_NORMAL_TABLE_MAX) {
-            ent_fn.assign(desc->num_entities, -1);
-            fn_tab.reserve(face_instances);
-            for (uint32_t e = 0; e < desc->num_entities; ++e) {
-                const igx_entity& en = desc->entities[e];
-                const igx_shape& sh = desc->shapes[en.shape];
-                if (sh.type != IGX_SHAPE_TRIMESH || sh.mesh < 0) continue;
-                const igx_mesh& m = desc->meshes[sh.mesh];
-                ent_fn[e] = (int)fn_tab.size();
-                const float* T = en.to_global;
-                auto xf = [&](uint32_t v, float out[3]) {
-                    const float* p = m.vertices + 3 * v;
-                    for (int r = 0; r < 3; ++r) {
-                        float acc = T[r * 4 + 0] * p[0];
-                        acc = acc + T[r * 4 + 1] * p[1];
-                        acc = acc + T[r * 4 + 2] * p[2];
-                        out[r] = acc + T[r * 4 + 3];
-                    }
-                };
-                for (uint32_t f = 0; f < m.num_faces; ++f) {
-                    float v0[3], v1[3], v2[3];
-                    xf(m.indices[3 * f], v0);
-                    xf(m.indices[3 * f + 1], v1);
-                    xf(m.indices[3 * f + 2], v2);
-                    const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]};
-                    const float e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
-                    const float n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-                    float nn2 = n[0] * n[0];
-                    nn2 = nn2 + n[1] * n[1];
-                    nn2 = nn2 + n[2] * n[2];
-                    const float inv = 1 / std::sqrt(nn2);
-                    fn_tab.push_back(make_float4(n[0] * inv, n[1] * inv, n[2] * inv, 0));
-                }
-            }
-        }
-        // the entity's face-normal offset in row 3 .w of its record, read
-        // with the normal matrix by surface_element's fsh path (-1: none)
-        for (uint32_t e = 0; e < desc->num_entities; ++e) {
-            const int off = ent_fn.empty() ? -1 : ent_fn[e];
-            std::memcpy(&ent[ENT_STRIDE * e + 3].w, &off, 4);
-        }
-    }
-
-    // ---- materials and lights (infinite lights first) --------------------
-    std::vector<int> light_remap(desc->num_lights, -1);
-    std::vector<DevLight> lights;
-    for (int pass = 0; pass < 2; ++pass)
-        for (uint32_t l = 0; l < desc->num_lights; ++l) {
-            const igx_light& L = desc->lights[l];
-            bool infinite = L.type == IGX_LIGHT_ENV || L.type == IGX_LIGHT_DIRECTIONAL || L.type == IGX_LIGHT_SUN ||
-                            L.type == IGX_LIGHT_CIE; // a sky is infinite and not delta
-            if ((pass == 0) != infinite) continue;
-            DevLight d{};
-            d.type = L.type;
-            d.infinite = infinite ? 1 : 0;
-            d.delta = (L.type == IGX_LIGHT_POINT || L.type == IGX_LIGHT_SPOT || L.type == IGX_LIGHT_DIRECTIONAL ||
-                       L.type == IGX_LIGHT_SUN) ? 1 : 0;
-            for (int i = 0; i < 3; ++i) d.radiance[i] = L.radiance[i];
-            if (L.type == IGX_LIGHT_PLANE) {
-                // make_plane_area_emitter constants (light/area.art:107-115)
-                float xa[3] = {L.x_axis[0], L.x_axis[1], L.x_axis[2]};
-                float ya[3] = {L.y_axis[0], L.y_axis[1], L.y_axis[2]};
-                float width = std::sqrt(xa[0] * xa[0] + xa[1] * xa[1] + xa[2] * xa[2]);
-                float height = std::sqrt(ya[0] * ya[0] + ya[1] * ya[1] + ya[2] * ya[2]);
-                float iw = 1 / width, ih = 1 / height;
-                for (int i = 0; i < 3; ++i) {
-                    d.origin[i] = L.origin[i];
-                    d.ex[i] = xa[i] * iw;
-                    d.ey[i] = ya[i] * ih;
-                    d.normal[i] = L.normal[i];
-                }
-                d.origin[3] = width;
-                d.ex[3] = height;
-                d.ey[3] = 1 / L.area;
-                d.normal[3] = L.area;
-            } else if (L.type == IGX_LIGHT_POINT) {
-                for (int i = 0; i < 3; ++i) d.origin[i] = L.origin[i];
-            } else if (L.type == IGX_LIGHT_SPOT) {
-                for (int i = 0; i < 3; ++i) { d.origin[i] = L.origin[i]; d.normal[i] = L.normal[i]; }
-                float cc = std::cos(L.cutoff), cf = std::cos(L.falloff);
-                d.spot[0] = cc;
-                d.spot[1] = cf;
-                d.spot[2] = cf - cc;
-            } else if (L.type == IGX_LIGHT_DIRECTIONAL) {
-                for (int i = 0; i < 3; ++i) d.normal[i] = L.normal[i];
-            } else if (L.type == IGX_LIGHT_SUN) {
-                // make_sun_light constants (light/sun.art:4-8)
-                for (int i = 0; i < 3; ++i) d.normal[i] = L.normal[i];
-                float c = L.cutoff;
-                float r = std::sqrt(1 - c * c) / c; // sun_radius_from_cos_angle
-                d.spot[0] = c;
-                d.spot[1] = 3.14159265359f * r * r;
-            } else if (L.type == IGX_LIGHT_SPHERE || L.type == IGX_LIGHT_MESH) {
-                if (L.entity < 0 || (uint32_t)L.entity >= desc->num_entities)
-                    return fail(dev, IGX_ERR_INVALID_ARGUMENT, "area light references an invalid entity");
-                d.entity = L.entity;
-                if (L.type == IGX_LIGHT_SPHERE) {
-                    if (!(L.area > 0) || !(L.radius > 0))
-                        return fail(dev, IGX_ERR_INVALID_ARGUMENT, "sphere light needs a positive radius and area");
-                    for (int i = 0; i < 3; ++i) d.origin[i] = L.origin[i];
-                    d.origin[3] = L.radius;
-                    d.spot[0] = L.area;
-                } else {
-                    const igx_shape& sh = desc->shapes[desc->entities[L.entity].shape];
-                    if (sh.type != IGX_SHAPE_TRIMESH || sh.mesh < 0 || desc->meshes[sh.mesh].num_faces == 0)
-                        return fail(dev, IGX_ERR_INVALID_ARGUMENT, "mesh light needs a non-empty triangle entity");
-                    d.spot[0] = (float)desc->meshes[sh.mesh].num_faces;
-                }
-            } else if (L.type == IGX_LIGHT_CIE) {
-                if (L.sky_kind < IGX_SKY_UNIFORM || L.sky_kind > IGX_SKY_INTERMEDIATE)
-                    return fail(dev, IGX_ERR_INVALID_ARGUMENT, "invalid CIE sky kind");
-                static_assert(offsetof(DevLight, radiance) == 16 && sizeof(DevLight) == 16 + sizeof(CieSky), "CieSky lives behind the DevLight header");
-                const CieSky sky = make_cie_sky(L);
-                std::memcpy(d.radiance, &sky, sizeof(sky));
-            } else if (L.type != IGX_LIGHT_ENV) {
-                return fail(dev, IGX_ERR_UNSUPPORTED, "unsupported light type");
-            }
-            light_remap[l] = (int)lights.size();
-            lights.push_back(d);
-        }
-    int num_infinite = 0;
-    for (auto& l : lights) num_infinite += l.infinite;
-    // NEE selector tables over the finite lights, in device order (host/light_select.h)
-    std::vector<igx_light> finite_lights;
-    for (uint32_t l = 0; l < desc->num_lights; ++l)
-        if (light_remap[l] >= num_infinite) finite_lights.push_back(desc->lights[l]);
-    // (pass 1 above numbers the finite lights in desc order, so this is device order)
-    const igx::LightSelectTables lsel = igx::build_light_select(desc->technique.light_selector, (int)lights.size(), finite_lights);
-    std::vector<DevMaterial> mats(desc->num_materials);
-    for (uint32_t i = 0; i < desc->num_materials; ++i) {
-        const igx_material& m = desc->materials[i];
-        DevMaterial d{};
-        switch (m.bsdf_type) {
-        case IGX_BSDF_DIFFUSE: d.type = MAT_DIFFUSE; break;
-        case IGX_BSDF_DIELECTRIC: d.type = MAT_DIELECTRIC; break;
-        case IGX_BSDF_CONDUCTOR: d.type = MAT_CONDUCTOR; break;
-        case IGX_BSDF_PLASTIC: d.type = MAT_PLASTIC; break;
-        case IGX_BSDF_PRINCIPLED: d.type = MAT_PRINCIPLED; break;
-        default: return fail(dev, IGX_ERR_UNSUPPORTED, "unsupported bsdf type " + std::to_string(m.bsdf_type));
-        }
-        if (m.distribution < IGX_MICROFACET_DELTA || m.distribution > IGX_MICROFACET_BECKMANN)
-            return fail(dev, IGX_ERR_INVALID_ARGUMENT, "invalid microfacet distribution");
-        d.light = m.light >= 0 && (uint32_t)m.light < desc->num_lights ? light_remap[m.light] : -1;
-        // check_if_delta_distribution (core/microfacet.art:272): alpha <= 1e-4 is a delta lobe
-        const bool rough = m.distribution != IGX_MICROFACET_DELTA && m.alpha_u > 1e-4f && m.alpha_v > 1e-4f;
-        d.dist = rough ? m.distribution : MF_DELTA;
-        bool mirror = true; // make_conductor_bsdf: eta ~ black and k ~ white (bsdf/conductor.art:111-121)
-        for (int c = 0; c < 3; ++c) {
-            d.kd[c] = m.kd[c];
-            d.ks[c] = m.ks[c];
-            d.kt[c] = m.kt[c];
-            d.eta[c] = m.eta[c];
-            d.kappa[c] = m.kappa[c];
-            mirror = mirror && std::fabs(m.eta[c]) <= 1e-4f && std::fabs(m.kappa[c] - 1.0f) <= 1e-4f;
-        }
-        d.mirror = mirror ? 1 : 0;
-        if (m.bsdf_type == IGX_BSDF_DIELECTRIC) d.mirror = m.thin ? 1 : 0; // dielectric: thin flag
-        d.kd[3] = m.bsdf_type == IGX_BSDF_DIFFUSE ? m.diffuse_alpha : 0.0f;
-        d.ks[3] = m.ext_ior;
-        d.kt[3] = m.int_ior;
-        d.eta[3] = m.alpha_u;
-        d.kappa[3] = m.alpha_v;
-        if (m.texture == IGX_TEXTURE_CHECKER && m.bsdf_type == IGX_BSDF_DIFFUSE) {
-            const int32_t kind = IGX_TEXTURE_CHECKER;
-            std::memcpy(&d.pad[0], &kind, 4);
-            d.pad[1] = m.tex_scale;
-            for (int c = 0; c < 3; ++c) d.pad[2 + c] = m.tex_kd1[c];
-        } else if (m.texture != IGX_TEXTURE_NONE) {
-            return fail(dev, IGX_ERR_UNSUPPORTED, "texture " + std::to_string(m.texture) + " on this bsdf type");
-        }
-        if (m.bsdf_type == IGX_BSDF_PRINCIPLED) {
-            // packing of the principled closure (igx_kernels.h, principled_of)
-            DevMaterial q{};
-            q.type = MAT_PRINCIPLED;
-            q.light = d.light;
-            q.dist = MF_VNDF_GGX;
-            q.mirror = (m.thin ? 1 : 0) | (m.clearcoat_top_only ? 2 : 0);
-            for (int c = 0; c < 3; ++c) q.kd[c] = m.kd[c];
-            q.kd[3] = m.ior;
-            q.ks[0] = m.diffuse_transmission;
-            q.ks[1] = m.specular_transmission;
-            q.ks[2] = m.specular_tint;
-            q.ks[3] = m.alpha_u;
-            q.kt[0] = m.alpha_v;
-            q.kt[1] = m.flatness;
-            q.kt[2] = m.metallic;
-            q.kt[3] = m.sheen;
-            q.eta[0] = m.sheen_tint;
-            q.eta[1] = m.clearcoat;
-            q.eta[2] = m.clearcoat_gloss;
-            q.eta[3] = m.clearcoat_roughness;
-            d = q;
-        }
-        mats[i] = d;
-    }
-
-    // hot nodes first: any prefix of the node array is a treelet (stage_treelet)
-    order_hot_nodes(nodes, quantize ? 5 : width, inst, tlas_root, TREELET_FRONT);
-
-    // ---- upload ----------------------------------------------------------
     SceneView sv{};
-    igx_status st;
-    if ((st = upload(dev, nodes, &sv.nodes)) || (st = upload(dev, tris, &sv.tris)) || (st = upload(dev, inst, &sv.inst)) ||
-        (st = upload(dev, spheres, &sv.spheres)) || (st = upload(dev, ent, &sv.ent)) || (st = upload(dev, vtx, &sv.vtx)) ||
-        (st = upload(dev, nrm, &sv.nrm)) || (st = upload(dev, idx, &sv.idx)) || (st = upload(dev, mats, &sv.mats)) ||
-        (st = upload(dev, lights, &sv.lights)) || (st = upload(dev, lsel.cdf, &sv.sel_cdf)) ||
-        (st = upload(dev, lsel.hierarchy, &sv.sel_tree)) || (st = upload(dev, ent_enc, &sv.ent_enc)) ||
-        (st = upload(dev, enc_tab, &sv.enc)) || (st = upload(dev, enc_box, &sv.enc_box)) || (st = upload(dev, ent_fn, &sv.ent_fn)) ||
-        (st = upload(dev, fn_tab, &sv.fn_tab)) || (st = upload(dev, uvs, &sv.uv)) || (st = upload(dev, fsh, &sv.fsh))) {
+    if ((st = upload(dev, t.nodes, &sv.nodes)) || (st = upload(dev, t.tris, &sv.tris)) || (st = upload(dev, t.inst, &sv.inst)) ||
+        (st = upload(dev, t.spheres, &sv.spheres)) || (st = upload(dev, t.ent, &sv.ent)) || (st = upload(dev, t.vtx, &sv.vtx)) ||
+        (st = upload(dev, t.nrm, &sv.nrm)) || (st = upload(dev, t.idx, &sv.idx)) || (st = upload(dev, t.mats, &sv.mats)) ||
+        (st = upload(dev, t.lights, &sv.lights)) || (st = upload(dev, t.lsel.cdf, &sv.sel_cdf)) ||
+        (st = upload(dev, t.lsel.hierarchy, &sv.sel_tree)) || (st = upload(dev, t.ent_enc, &sv.ent_enc)) ||
+        (st = upload(dev, t.enc_tab, &sv.enc)) || (st = upload(dev, t.enc_box, &sv.enc_box)) ||
+        (st = upload(dev, t.ent_fn, &sv.ent_fn)) || (st = upload(dev, t.fn_tab, &sv.fn_tab)) || (st = upload(dev, t.uvs, &sv.uv)) ||
+        (st = upload(dev, t.fsh, &sv.fsh))) {
         free_scene(dev);
         return st;
     }
-    if (fn_tab.empty()) sv.fn_tab = nullptr; // surface_element computes the normals
-    if (fsh.empty()) sv.fsh = nullptr;       // ... reads the index and normal tables
-    if (uvs.empty()) sv.uv = nullptr;
-    sv.tlas_root = tlas_root;
-    sv.num_nodes = (int)(nodes.size() / nf4);
-    sv.node_f4 = nf4;
-    dev->bvh_width = width;
-    dev->quantized = quantize;
-    dev->nf4 = nf4;
-    sv.num_inst = (int)(inst.size() / 4);
-    sv.num_enc = (int)enc_tab.size();
-    sv.num_tris = (int)(tris.size() / 3);
-    {
-        size_t b = ((size_t)sv.num_nodes * nf4 + (size_t)sv.num_inst * 4 + (size_t)sv.num_tris * 3) * 16;
-        dev->table_bytes = b; // the LDS layout (stage_scene_lds) is the same tables back to back; configure_lds below
-        sv.num_ent = (int)(ent.size() / ENT_STRIDE);
-        sv.num_fsh = (int)(fsh.size() / 3);
-        sv.num_fn = (int)fn_tab.size();
-        sv.num_mats = (int)mats.size();
-        dev->lds_shading_tab[LDS_TAB_ENT] = ent.size() * sizeof(ent[0]);
-        dev->lds_shading_tab[LDS_TAB_FSH] = fsh.size() * sizeof(fsh[0]);
-        dev->lds_shading_tab[LDS_TAB_FN] = fn_tab.size() * sizeof(fn_tab[0]);
-        dev->lds_shading_tab[LDS_TAB_MATS] = mats.size() * sizeof(DevMaterial);
-        dev->lds_shading_tab[LDS_TAB_LIGHTS] = lights.size() * sizeof(lights[0]);
-        dev->lds_shading_tab[LDS_TAB_ENT_ENC] = ent_enc.size() * sizeof(ent_enc[0]);
-        dev->shading_bytes = ent.size() * sizeof(ent[0]) + vtx.size() * sizeof(vtx[0]) + nrm.size() * sizeof(nrm[0]) +
-                             idx.size() * sizeof(idx[0]) + mats.size() * sizeof(DevMaterial) + lights.size() * sizeof(lights[0]) +
-                             fn_tab.size() * sizeof(fn_tab[0]) + fsh.size() * sizeof(fsh[0]);
-    }
-    sv.num_lights = (int)lights.size();
-    sv.num_infinite = num_infinite;
-    sv.selector = lsel.selector;
-    // bbox_radius(scene_bbox) * 1.01 (light/env.art:75; core/bbox.art:24)
-    float dx = desc->scene_bbox_max[0] - desc->scene_bbox_min[0];
-    float dy = desc->scene_bbox_max[1] - desc->scene_bbox_min[1];
-    float dz = desc->scene_bbox_max[2] - desc->scene_bbox_min[2];
-    sv.scene_radius = std::sqrt(dx * dx + dy * dy + dz * dz) / 2 * 1.01f;
-    if (desc->technique.max_depth > 255) {
-        free_scene(dev);
-        return fail(dev, IGX_ERR_UNSUPPORTED, "max_depth above 255 is not supported (8-bit path depth)");
-    }
+    if (t.fn_tab.empty()) sv.fn_tab = nullptr; // surface_element computes the normals
+    if (t.fsh.empty()) sv.fsh = nullptr;       // ... reads the index and normal tables
+    if (t.uvs.empty()) sv.uv = nullptr;
+    sv.tlas_root = t.tlas_root;
+    sv.num_nodes = (int)(t.nodes.size() / t.nf4);
+    sv.node_f4 = t.nf4;
+    sv.num_inst = (int)(t.inst.size() / 4);
+    sv.num_enc = (int)t.enc_tab.size();
+    sv.num_tris = (int)(t.tris.size() / 3);
+    sv.num_ent = (int)(t.ent.size() / ENT_STRIDE);
+    sv.num_fsh = (int)(t.fsh.size() / 3);
+    sv.num_fn = (int)t.fn_tab.size();
+    sv.num_mats = (int)t.mats.size();
+    sv.num_lights = (int)t.lights.size();
+    sv.num_infinite = t.num_infinite;
+    sv.selector = t.lsel.selector;
+    sv.scene_radius = t.scene_radius;
     sv.max_depth = desc->technique.max_depth;
     sv.min_depth = desc->technique.min_depth;
     sv.nee = desc->technique.nee;
     sv.clamp = desc->technique.clamp;
+    dev->sv = sv;
+    dev->bvh_width = t.width;
+    dev->quantized = t.quantized;
+    dev->nf4 = t.nf4;
+    // the LDS layout (stage_scene_lds) is the traversal tables back to back; configure_lds below
+    dev->table_bytes = ((size_t)sv.num_nodes * t.nf4 + (size_t)sv.num_inst * 4 + (size_t)sv.num_tris * 3) * 16;
+    dev->lds_shading_tab[LDS_TAB_ENT] = t.ent.size() * sizeof(t.ent[0]);
+    dev->lds_shading_tab[LDS_TAB_FSH] = t.fsh.size() * sizeof(t.fsh[0]);
+    dev->lds_shading_tab[LDS_TAB_FN] = t.fn_tab.size() * sizeof(t.fn_tab[0]);
+    dev->lds_shading_tab[LDS_TAB_MATS] = t.mats.size() * sizeof(DevMaterial);
+    dev->lds_shading_tab[LDS_TAB_LIGHTS] = t.lights.size() * sizeof(t.lights[0]);
+    dev->lds_shading_tab[LDS_TAB_ENT_ENC] = t.ent_enc.size() * sizeof(t.ent_enc[0]);
+    dev->shading_bytes = t.ent.size() * sizeof(t.ent[0]) + t.vtx.size() * sizeof(t.vtx[0]) + t.nrm.size() * sizeof(t.nrm[0]) +
+                         t.idx.size() * sizeof(t.idx[0]) + t.mats.size() * sizeof(DevMaterial) +
+                         t.lights.size() * sizeof(t.lights[0]) + t.fn_tab.size() * sizeof(t.fn_tab[0]) +
+                         t.fsh.size() * sizeof(t.fsh[0]);
     dev->cam_desc = desc->camera;
     dev->rays_w = desc->film_width;
     dev->rays_h = desc->film_height;
     dev->rays_frame = dev->rays_seed = 0;
-    dev->aov_on = desc->technique.aov_mis != 0;
-    dev->sv = sv;
-    // stack: TLAS pushes + BLAS pushes (the depth for BVH2) + marker + resume entry + exit sentinel
-#ifndef IGX_STACK_SLACK
-#define IGX_STACK_SLACK 0
-#endif
-    dev->scene_depth = tlas_depth + blas_depth + 3 + IGX_STACK_SLACK;
-    if (dev->scene_depth > MAX_STACK) {
-        free_scene(dev);
-        return fail(dev, IGX_ERR_UNSUPPORTED, "BVH too deep for the traversal stack (" + std::to_string(dev->scene_depth) + " entries)");
-    }
-    // shading feature set (variant bit 2): beyond Lambert + dielectric and the
-    // plane/env/point/spot/directional/sun lights
-    dev->full_shading = dev->full_shading_opt;
-    for (uint32_t i = 0; i < desc->num_materials; ++i) {
-        const igx_material& m = desc->materials[i];
-        if (m.bsdf_type == IGX_BSDF_CONDUCTOR || m.bsdf_type == IGX_BSDF_PLASTIC || m.bsdf_type == IGX_BSDF_PRINCIPLED ||
-            (m.bsdf_type == IGX_BSDF_DIFFUSE && m.diffuse_alpha > 1.1920929e-7f))
-            dev->full_shading = true;
-    }
-    for (uint32_t l = 0; l < desc->num_lights; ++l)
-        if (desc->lights[l].type == IGX_LIGHT_SPHERE || desc->lights[l].type == IGX_LIGHT_MESH) dev->full_shading = true;
-    if (textured) dev->full_shading = true; // textures are looked up by the full shading variant only
-    if (dev->aov_on) dev->full_shading = true; // so are the MIS AOVs (add_aov)
-    // and every camera but the pinhole perspective one (gen_pixel), and the CIE skies
-    if (camera_needs_full(desc->camera)) dev->full_shading = true;
-    for (uint32_t l = 0; l < desc->num_lights; ++l)
-        if (desc->lights[l].type == IGX_LIGHT_CIE) dev->full_shading = true;
-    for (uint32_t e = 0; textured && e < desc->num_entities; ++e) {
-        const igx_entity& en = desc->entities[e];
-        if (desc->materials[en.material].texture != IGX_TEXTURE_NONE && desc->shapes[en.shape].type == IGX_SHAPE_SPHERE) {
-            free_scene(dev);
-            return fail(dev, IGX_ERR_UNSUPPORTED, "textured material on an analytic sphere (texture coordinates of spheres are not supported)");
-        }
-    }
+    dev->aov_on = t.aov_on;
+    dev->scene_depth = t.scene_depth;
+    dev->full_shading = t.full_shading;
     if ((st = configure_stack(dev)) != IGX_OK) {
         free_scene(dev);
         return st;

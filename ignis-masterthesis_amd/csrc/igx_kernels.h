@@ -38,7 +38,7 @@ struct SceneView {
     // alignment holes, so every other field keeps its offset and the basic
     // variant's kernels their code.
     int cam_type;          // IGX_CAMERA_*
-    // treelet: nodes [0, tree_n) of `nodes` (the hottest, igx_upload_scene's
+    // treelet: nodes [0, tree_n) of `nodes` (the hottest, order_hot_nodes'
     // hot order) staged in LDS at `tree` by stage_treelet (variant_tree kernels)
     const float4* tree;
     int tree_n;
@@ -88,7 +88,6 @@ __host__ __device__ inline void set_camera(SceneView& sv, const CameraModel& m) 
 // The enclosing entities' world boxes (path / shadow-ray classes, read by
 // every lane at every append): a small LDS copy, so the class test does not
 // wait on dependent global loads (they cost k_extend ~10 % of its wave time).
-constexpr int MAX_ENC_BOXES = 32;
 template <int BLOCK_>
 __device__ __forceinline__ const float4* stage_enc_boxes(const SceneView& sv) {
     __shared__ float4 enc_box_lds[2 * MAX_ENC_BOXES];
@@ -201,17 +200,10 @@ constexpr uint32_t RAY_CAMERA = 0x1, RAY_LIGHT = 0x2, RAY_BOUNCE = 0x4, RAY_SHAD
 #ifndef IGX_IDENTITY_INSTANCES
 #define IGX_IDENTITY_INSTANCES 1
 #endif
-// instance record flag (info.w, next to the visibility bits): the trimesh
-// instance's to_local is the identity, so its entity-space ray is the world
-// ray (instance_test skips the transform; set by igx_upload_scene)
-constexpr uint32_t INST_IDENTITY = 1u << 30;
-// ... or a pure translation (rows (1 0 0 tx), (0 1 0 ty), (0 0 1 tz)): the
-// entity-space ray is (o + t, d), so its reciprocal direction is the world
-// ray's (IGX_TRANSLATE_INSTANCES)
+// the instance-record shortcuts (INST_IDENTITY, INST_TRANSLATE in device_scene.h)
 #ifndef IGX_TRANSLATE_INSTANCES
 #define IGX_TRANSLATE_INSTANCES 1
 #endif
-constexpr uint32_t INST_TRANSLATE = 1u << 29;
 // the identity / translation shortcuts give transform_ray's direction bit for
 // bit when no component is zero (with x != 0: 1*x + 0*y + 0*z == x)
 __device__ __forceinline__ bool shortcut_dir_ok(f3 d) { return d.x != 0.0f && d.y != 0.0f && d.z != 0.0f; }
@@ -855,7 +847,7 @@ __device__ __forceinline__ bool trace_ray(const SceneView& sv, f3 o, f3 d, float
 
 // Closest hit of a ray that travels inside enclosing entity number `enc` (a closed,
 // non-thin dielectric mesh whose world box keeps a margin from every other
-// entity's box, igx_upload_scene).  The ray starts on the entity's surface,
+// entity's box, build_scene_tables).  The ray starts on the entity's surface,
 // i.e. in its box; along the ray the box is one interval from the start, every
 // hit on the entity lies in it and every other entity lies beyond it.  So a
 // hit the entity's BLAS finds is the closest hit of the whole scene -- the
