@@ -17,6 +17,13 @@ struct float4_ { float x, y, z, w; };
 #define IGX_SCENE_HD
 #endif
 
+// Order of the local pixel index: 1 = 4 x 2 pixel blocks where the width (tile
+// side) allows, 0 = row-major (local_to_global in igx_device.hip; the host
+// counts a chunk's film pixels in the same order, host/render_plan.h)
+#ifndef IGX_PIXEL_BLOCKS
+#define IGX_PIXEL_BLOCKS 1
+#endif
+
 namespace igxd {
 
 // Traversal encodings (see host/bvh_build.h)

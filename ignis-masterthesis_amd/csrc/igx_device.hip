@@ -30,6 +30,7 @@
 #include "../host/scene_tables.h"
 #include "../host/lds_plan.h"
 #include "../host/extend_shape.h"
+#include "../host/render_plan.h"
 #include "../host/aov_plan.h"
 #include "../host/film_tools.h"
 
@@ -79,7 +80,7 @@ constexpr int BLOCK_WIDE = LDS_PLAN_BLOCK_WIDE;
 static_assert(BLOCK == LDS_PLAN_BLOCK, "host/lds_plan.h plans for BLOCK-thread blocks");
 [[maybe_unused]] constexpr int MAX_BLOCKS_PER_CU = 8;  // 2048 threads per CU; grids never exceed num_cus * this
 constexpr int MAX_BOUNCES = 256;          // path depth is stored in 8 bits (p1.w, above the 24-bit RNG counter)
-constexpr long long MAX_CHUNK_PATHS = 1ll << 27; // paths per chunk (one wavefront), ~25 GB of stream buffers per slot
+// MAX_CHUNK_PATHS (paths per chunk, one wavefront) lives in host/render_plan.h
 // a path's slot in its chunk takes the low 27 bits of the slot word; the top
 // 5 carry 1 + the index of the enclosing entity it is in (at most MAX_ENCLOSING)
 constexpr int SLOT_BITS = 27;
@@ -212,9 +213,7 @@ __device__ __forceinline__ void slot_coords(const FrameArgs& fa, int slot, int& 
 // camera rays then diverge less in the traversal (IGX_PIXEL_BLOCKS).  Every
 // user of the index (generation, resolve, tile packing) maps it here, and a
 // path's arithmetic depends on its pixel only, so the film is the same.
-#ifndef IGX_PIXEL_BLOCKS
-#define IGX_PIXEL_BLOCKS 1
-#endif
+// (the macro's default: device_scene.h, shared with host/render_plan.h)
 __device__ __forceinline__ void block_order(int r, int w, int& x, int& y) {
     const int pair = r / (2 * w), q = r - pair * 2 * w; // row pair, index in it
     x = (q >> 3) * 4 + (q & 3);
@@ -2456,6 +2455,24 @@ inline bool use_shadow_optimistic(const igx_device* dev, bool split, bool aovs) 
     return dev->shadow_optimistic_opt > 0 || (dev->shadow_classes_opt && dev->sv.num_enc > 0);
 }
 
+// Where a chunk's launches go: the stream of its bounces, of its tail kernel
+// and of its shadow kernels (the main stream again unless they overlap the
+// next bounce's trace), the spill columns that go with each stream, and the
+// camera of the chunk's render call.  The launch helpers take all of it from
+// here, none of it from the handle.
+struct LaunchCtx {
+    hipStream_t main, tail, shadow;
+    int *spill_main, *spill_tail, *spill_shadow;
+    CameraModel cam;
+};
+// the scene view of a launch on the stream whose spill columns are `spill`
+inline SceneView launch_view(const igx_device* dev, const LaunchCtx& ctx, int* spill) {
+    SceneView sv = dev->sv;
+    set_camera(sv, ctx.cam);
+    sv.spill = spill;
+    return sv;
+}
+
 // Launch helpers dispatching on the scene's traversal variant.
 // (bit 7, VARIANT_Q4: quantised 4-wide nodes, only with bit 1)
 #define IGX_DISPATCH_VARIANT(v, MACRO)        \
@@ -2492,10 +2509,11 @@ inline bool use_shadow_optimistic(const igx_device* dev, bool split, bool aovs) 
 // traversal tables): its launch, its resident blocks per CU and the
 // one-time raise of its dynamic-LDS limit (a block above 64 KB needs it).
 template <bool STATS>
-void launch_extend_wide(igx_device* dev, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in, const PathBuf& out,
-                        const KernelCounters& kc, int tail) {
+void launch_extend_wide(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in,
+                        const PathBuf& out, const KernelCounters& kc, int tail) {
     const size_t dyn = lds_pad16(dev->lds_scene_bytes) + dev->lds_shading_bytes;
-#define L_EXTW(S) hipLaunchKernelGGL((k_extend<S, STATS, true, BLOCK_WIDE>), dim3(grid), dim3(BLOCK_WIDE), dyn, dev->stream, fa, dev->sv, in, out, s.sh, s.L, kc, tail)
+    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
+#define L_EXTW(S) hipLaunchKernelGGL((k_extend<S, STATS, true, BLOCK_WIDE>), dim3(grid), dim3(BLOCK_WIDE), dyn, ctx.main, fa, sv, in, out, s.sh, s.L, kc, tail)
     IGX_DISPATCH_VARIANT8(dev->variant, L_EXTW);
 #undef L_EXTW
 }
@@ -2528,25 +2546,26 @@ hipError_t extend_wide_prepare(int v, size_t dyn) {
 // launch bounds and static LDS with the generic instantiation of their
 // layout, so grids and the treelet are sized by the generic kernel's
 // resident blocks.
-void launch_extend_shaped_wide(igx_device* dev, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa, const PathBuf& in,
-                               const PathBuf& out, const KernelCounters& kc, int tail);
+void launch_extend_shaped_wide(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa,
+                               const PathBuf& in, const PathBuf& out, const KernelCounters& kc, int tail);
 hipError_t extend_shaped_wide_prepare(int v, size_t dyn);
-void launch_extend_shaped_lds(igx_device* dev, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa, const PathBuf& in,
-                              const PathBuf& out, const KernelCounters& kc, int tail);
-void launch_extend_shaped_global(igx_device* dev, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa, const PathBuf& in,
-                                 const PathBuf& out, const KernelCounters& kc, int tail);
+void launch_extend_shaped_lds(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa,
+                              const PathBuf& in, const PathBuf& out, const KernelCounters& kc, int tail);
+void launch_extend_shaped_global(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa,
+                                 const PathBuf& in, const PathBuf& out, const KernelCounters& kc, int tail);
 #define IGX_SHAPED(S, LDS_, BT_, dyn_, sv_)                                                                                        \
     if (shape == EXTEND_GENERATE)                                                                                                  \
-        hipLaunchKernelGGL((k_extend<S, false, LDS_, BT_, EXTEND_GENERATE>), dim3(grid), dim3(BT_), dyn_, dev->stream, fa, sv_, in, \
+        hipLaunchKernelGGL((k_extend<S, false, LDS_, BT_, EXTEND_GENERATE>), dim3(grid), dim3(BT_), dyn_, ctx.main, fa, sv_, in,    \
                            out, s.sh, s.L, kc, tail);                                                                              \
     else                                                                                                                           \
-        hipLaunchKernelGGL((k_extend<S, false, LDS_, BT_, EXTEND_BOUNCE>), dim3(grid), dim3(BT_), dyn_, dev->stream, fa, sv_, in,   \
+        hipLaunchKernelGGL((k_extend<S, false, LDS_, BT_, EXTEND_BOUNCE>), dim3(grid), dim3(BT_), dyn_, ctx.main, fa, sv_, in,      \
                            out, s.sh, s.L, kc, tail)
 #if IGX_PART == 7
-void launch_extend_shaped_wide(igx_device* dev, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa, const PathBuf& in,
-                               const PathBuf& out, const KernelCounters& kc, int tail) {
+void launch_extend_shaped_wide(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa,
+                               const PathBuf& in, const PathBuf& out, const KernelCounters& kc, int tail) {
     const size_t dyn = lds_pad16(dev->lds_scene_bytes) + dev->lds_shading_bytes;
-#define L_EXTW(S) IGX_SHAPED(S, true, BLOCK_WIDE, dyn, dev->sv)
+    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
+#define L_EXTW(S) IGX_SHAPED(S, true, BLOCK_WIDE, dyn, sv)
     IGX_DISPATCH_VARIANT8(dev->variant, L_EXTW);
 #undef L_EXTW
 }
@@ -2562,17 +2581,18 @@ hipError_t extend_shaped_wide_prepare(int v, size_t dyn) {
 }
 #endif
 #if IGX_PART == 8
-void launch_extend_shaped_lds(igx_device* dev, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa, const PathBuf& in,
-                              const PathBuf& out, const KernelCounters& kc, int tail) {
-#define L_EXTL(S) IGX_SHAPED(S, true, BLOCK, dev->lds_scene_bytes, dev->sv)
+void launch_extend_shaped_lds(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa,
+                              const PathBuf& in, const PathBuf& out, const KernelCounters& kc, int tail) {
+    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
+#define L_EXTL(S) IGX_SHAPED(S, true, BLOCK, dev->lds_scene_bytes, sv)
     IGX_DISPATCH_VARIANT8(dev->variant, L_EXTL);
 #undef L_EXTL
 }
 #endif
 #if IGX_PART == 9
-void launch_extend_shaped_global(igx_device* dev, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa, const PathBuf& in,
-                                 const PathBuf& out, const KernelCounters& kc, int tail) {
-    SceneView tsv = dev->sv;
+void launch_extend_shaped_global(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa,
+                                 const PathBuf& in, const PathBuf& out, const KernelCounters& kc, int tail) {
+    SceneView tsv = launch_view(dev, ctx, ctx.spill_main);
     tsv.tree_n = dev->tree_ext;
 #define L_EXT(S) IGX_SHAPED(S, false, BLOCK, tree_bytes(dev, tsv.tree_n), tsv)
     IGX_DISPATCH_VARIANT8(dev->variant, L_EXT);
@@ -2608,63 +2628,64 @@ inline ExtendShape launch_shape(const igx_device* dev, bool instrumented, const 
 }
 
 template <bool STATS>
-void launch_extend(igx_device* dev, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in, const PathBuf& out,
-                   const KernelCounters& kc, int tail) {
+void launch_extend(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in,
+                   const PathBuf& out, const KernelCounters& kc, int tail) {
     if (const ExtendShape shape = launch_shape(dev, STATS, fa, in, out, s.sh, kc); shape != EXTEND_GENERIC) {
         ++dev->stats.launches_extend_shaped[shape == EXTEND_GENERATE ? 0 : 1];
-        if (dev->ext_block == BLOCK_WIDE) launch_extend_shaped_wide(dev, s, grid, shape, fa, in, out, kc, tail);
-        else if (dev->lds_scene_bytes) launch_extend_shaped_lds(dev, s, grid, shape, fa, in, out, kc, tail);
-        else launch_extend_shaped_global(dev, s, grid, shape, fa, in, out, kc, tail);
+        if (dev->ext_block == BLOCK_WIDE) launch_extend_shaped_wide(dev, ctx, s, grid, shape, fa, in, out, kc, tail);
+        else if (dev->lds_scene_bytes) launch_extend_shaped_lds(dev, ctx, s, grid, shape, fa, in, out, kc, tail);
+        else launch_extend_shaped_global(dev, ctx, s, grid, shape, fa, in, out, kc, tail);
         return;
     }
     if (dev->ext_block == BLOCK_WIDE) {
-        launch_extend_wide<STATS>(dev, s, grid, fa, in, out, kc, tail);
+        launch_extend_wide<STATS>(dev, ctx, s, grid, fa, in, out, kc, tail);
         return;
     }
+    SceneView tsv = launch_view(dev, ctx, ctx.spill_main);
     if (dev->lds_scene_bytes) {
-#define L_EXTL(S) hipLaunchKernelGGL((k_extend<S, STATS, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, dev->stream, fa, dev->sv, in, out, s.sh, s.L, kc, tail)
+#define L_EXTL(S) hipLaunchKernelGGL((k_extend<S, STATS, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, ctx.main, fa, tsv, in, out, s.sh, s.L, kc, tail)
         IGX_DISPATCH_VARIANT8(dev->variant, L_EXTL);
 #undef L_EXTL
         return;
     }
-    SceneView tsv = dev->sv;
     tsv.tree_n = dev->tree_ext;
-#define L_EXT(S) hipLaunchKernelGGL((k_extend<S, STATS, false>), dim3(grid), dim3(BLOCK), tree_bytes(dev, tsv.tree_n), dev->stream, fa, tsv, in, out, s.sh, s.L, kc, tail)
+#define L_EXT(S) hipLaunchKernelGGL((k_extend<S, STATS, false>), dim3(grid), dim3(BLOCK), tree_bytes(dev, tsv.tree_n), ctx.main, fa, tsv, in, out, s.sh, s.L, kc, tail)
     IGX_DISPATCH_VARIANT8(dev->variant, L_EXT);
 #undef L_EXT
 }
 // k_trace (the split schedule without persistent lanes): 5 waves per SIMD on
 // global tables; LDS-staged tables set occupancy themselves
 template <bool STATS>
-void launch_trace(igx_device* dev, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in, const int* cnt, int tail,
-                  int* work) {
+void launch_trace(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in, const int* cnt,
+                  int tail, int* work) {
+    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
     if (use_refill(dev)) {
 #define L_TRR(S)                                                                                                        \
     if (dev->lds_scene_bytes)                                                                                            \
-        hipLaunchKernelGGL((k_trace_refill<S, STATS, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, dev->stream, fa, \
-                           dev->sv, in, s.hb, cnt, tail, dev->dstats, refill_min(dev), work);                            \
+        hipLaunchKernelGGL((k_trace_refill<S, STATS, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, ctx.main, fa,   \
+                           sv, in, s.hb, cnt, tail, dev->dstats, refill_min(dev), work);                                 \
     else                                                                                                                 \
-        hipLaunchKernelGGL((k_trace_refill<S, STATS, false>), dim3(grid), dim3(BLOCK), 0, dev->stream, fa, dev->sv, in, s.hb, \
+        hipLaunchKernelGGL((k_trace_refill<S, STATS, false>), dim3(grid), dim3(BLOCK), 0, ctx.main, fa, sv, in, s.hb,        \
                            cnt, tail, dev->dstats, refill_min(dev), work)
         IGX_DISPATCH_VARIANT(dev->variant, L_TRR);
 #undef L_TRR
         return;
     }
     if (dev->lds_scene_bytes) {
-#define L_TRL(S) hipLaunchKernelGGL((k_trace<S, STATS, 1, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, dev->stream, fa, dev->sv, in, s.hb, cnt, tail, dev->dstats)
+#define L_TRL(S) hipLaunchKernelGGL((k_trace<S, STATS, 1, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, ctx.main, fa, sv, in, s.hb, cnt, tail, dev->dstats)
         IGX_DISPATCH_VARIANT(dev->variant, L_TRL);
 #undef L_TRL
         return;
     }
-#define L_TR(S) hipLaunchKernelGGL((k_trace<S, STATS, 5, false>), dim3(grid), dim3(BLOCK), 0, dev->stream, fa, dev->sv, in, s.hb, cnt, tail, dev->dstats)
+#define L_TR(S) hipLaunchKernelGGL((k_trace<S, STATS, 5, false>), dim3(grid), dim3(BLOCK), 0, ctx.main, fa, sv, in, s.hb, cnt, tail, dev->dstats)
     IGX_DISPATCH_VARIANT(dev->variant, L_TR);
 #undef L_TR
 }
 template <bool STATS>
-void launch_shadow(igx_device* dev, Slot& s, int grid, const int* cnt, int* work, hipStream_t strm) {
-    SceneView tsv = dev->sv;
+void launch_shadow(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, const int* cnt, int* work) {
+    hipStream_t const strm = ctx.shadow;
+    SceneView tsv = launch_view(dev, ctx, ctx.spill_shadow); // its own columns where it overlaps the main stream's kernels
     tsv.tree_n = dev->tree_shadow;
-    if (strm != dev->stream) tsv.spill = dev->spill_shadow; // concurrent with the main stream's kernels
     if (use_refill(dev)) {
 #define L_SHR(S)                                                                                                        \
     if (dev->lds_scene_bytes)                                                                                            \
@@ -2693,23 +2714,23 @@ void launch_shadow(igx_device* dev, Slot& s, int grid, const int* cnt, int* work
 #undef L_SH
 }
 template <bool STATS>
-void launch_finish(igx_device* dev, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in, const int* cnt, int tail) {
-    SceneView tsv = dev->sv;
-    tsv.spill = dev->spill_tail; // k_finish runs concurrently with the main stream's kernels
-    tsv.tree_n = 0;              // the tail kernels stage no treelet
+void launch_finish(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in, const int* cnt,
+                   int tail) {
+    SceneView tsv = launch_view(dev, ctx, ctx.spill_tail); // k_finish may run concurrently with the main stream's kernels
+    tsv.tree_n = 0;                                        // the tail kernels stage no treelet
     if (dev->lds_scene_bytes) {
-#define L_FINL(S) hipLaunchKernelGGL((k_finish<S, STATS, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, dev->tail_stream, fa, tsv, in, s.L, cnt, tail, dev->dstats, dev->tail_counts)
+#define L_FINL(S) hipLaunchKernelGGL((k_finish<S, STATS, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, ctx.tail, fa, tsv, in, s.L, cnt, tail, dev->dstats, dev->tail_counts)
         IGX_DISPATCH_VARIANT8(dev->variant, L_FINL);
 #undef L_FINL
         return;
     }
     if (use_tail_pairs(dev)) {
-#define L_FINP(S) hipLaunchKernelGGL((k_finish_pairs<S, STATS>), dim3(grid), dim3(BLOCK), tree_bytes(dev, tsv.tree_n), dev->tail_stream, fa, tsv, in, s.L, cnt, tail, dev->dstats, dev->tail_counts)
+#define L_FINP(S) hipLaunchKernelGGL((k_finish_pairs<S, STATS>), dim3(grid), dim3(BLOCK), tree_bytes(dev, tsv.tree_n), ctx.tail, fa, tsv, in, s.L, cnt, tail, dev->dstats, dev->tail_counts)
         IGX_DISPATCH_VARIANT8(dev->variant, L_FINP);
 #undef L_FINP
         return;
     }
-#define L_FIN(S) hipLaunchKernelGGL((k_finish<S, STATS, false>), dim3(grid), dim3(BLOCK), tree_bytes(dev, tsv.tree_n), dev->tail_stream, fa, tsv, in, s.L, cnt, tail, dev->dstats, dev->tail_counts)
+#define L_FIN(S) hipLaunchKernelGGL((k_finish<S, STATS, false>), dim3(grid), dim3(BLOCK), tree_bytes(dev, tsv.tree_n), ctx.tail, fa, tsv, in, s.L, cnt, tail, dev->dstats, dev->tail_counts)
     IGX_DISPATCH_VARIANT8(dev->variant, L_FIN);
 #undef L_FIN
 }
@@ -2785,14 +2806,15 @@ int trace_blocks_per_cu(int v, size_t lds, bool refill) {
 #undef IGX_RESIDENT8
 #undef IGX_RESIDENT_G
 
-void launch_shade(igx_device* dev, bool full, int grid, const FrameArgs& fa, const PathBuf& in, const HitBuf& hb,
+void launch_shade(igx_device* dev, const LaunchCtx& ctx, bool full, int grid, const FrameArgs& fa, const PathBuf& in, const HitBuf& hb,
                   const PathBuf& out, const ShadowBuf& sh, float4* L, const KernelCounters& kc, int tail);
 int shade_blocks_per_cu(bool full);
 #if IGX_PART == 3
-void launch_shade(igx_device* dev, bool full, int grid, const FrameArgs& fa, const PathBuf& in, const HitBuf& hb,
+void launch_shade(igx_device* dev, const LaunchCtx& ctx, bool full, int grid, const FrameArgs& fa, const PathBuf& in, const HitBuf& hb,
                   const PathBuf& out, const ShadowBuf& sh, float4* L, const KernelCounters& kc, int tail) {
-    if (full) hipLaunchKernelGGL(k_shade<true>, dim3(grid), dim3(BLOCK), 0, dev->stream, fa, dev->sv, in, hb, out, sh, L, kc, tail);
-    else hipLaunchKernelGGL(k_shade<false>, dim3(grid), dim3(BLOCK), 0, dev->stream, fa, dev->sv, in, hb, out, sh, L, kc, tail);
+    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
+    if (full) hipLaunchKernelGGL(k_shade<true>, dim3(grid), dim3(BLOCK), 0, ctx.main, fa, sv, in, hb, out, sh, L, kc, tail);
+    else hipLaunchKernelGGL(k_shade<false>, dim3(grid), dim3(BLOCK), 0, ctx.main, fa, sv, in, hb, out, sh, L, kc, tail);
 }
 int shade_blocks_per_cu(bool full) { return full ? resident_blocks(k_shade<true>) : resident_blocks(k_shade<false>); }
 #endif
@@ -2844,19 +2866,19 @@ void launch_imageinfo(igx_device* dev, const float* film, int w, int h, float sc
 
 // Launch helpers: defined (explicitly instantiated) in their part, extern elsewhere.
 #define IGX_EXTEND_HELPERS(X, S)                                                                                     \
-    X void launch_extend<S>(igx_device*, Slot&, int, const FrameArgs&, const PathBuf&, const PathBuf&,               \
+    X void launch_extend<S>(igx_device*, const LaunchCtx&, Slot&, int, const FrameArgs&, const PathBuf&, const PathBuf&, \
                             const KernelCounters&, int);                                                             \
     X int extend_blocks_per_cu<S>(int, size_t, size_t);
 #define IGX_FINISH_HELPERS(X, S)                                                                                     \
-    X void launch_finish<S>(igx_device*, Slot&, int, const FrameArgs&, const PathBuf&, const int*, int);             \
+    X void launch_finish<S>(igx_device*, const LaunchCtx&, Slot&, int, const FrameArgs&, const PathBuf&, const int*, int); \
     X int finish_blocks_per_cu<S>(int, size_t, size_t, bool);
 #define IGX_TRACE_HELPERS(X, S)                                                                                      \
-    X void launch_trace<S>(igx_device*, Slot&, int, const FrameArgs&, const PathBuf&, const int*, int, int*);              \
-    X void launch_shadow<S>(igx_device*, Slot&, int, const int*, int*, hipStream_t);                                       \
+    X void launch_trace<S>(igx_device*, const LaunchCtx&, Slot&, int, const FrameArgs&, const PathBuf&, const int*, int, int*); \
+    X void launch_shadow<S>(igx_device*, const LaunchCtx&, Slot&, int, const int*, int*);                             \
     X int trace_blocks_per_cu<S>(int, size_t, bool);                                                                  \
     X int shadow_blocks_per_cu<S>(int, size_t, bool, size_t);
 #define IGX_EXTEND_WIDE_HELPERS(X, S)                                                                                \
-    X void launch_extend_wide<S>(igx_device*, Slot&, int, const FrameArgs&, const PathBuf&, const PathBuf&,          \
+    X void launch_extend_wide<S>(igx_device*, const LaunchCtx&, Slot&, int, const FrameArgs&, const PathBuf&, const PathBuf&, \
                                  const KernelCounters&, int);                                                        \
     X hipError_t extend_wide_prepare<S>(int, size_t);                                                                \
     X int extend_wide_blocks_per_cu<S>(int, size_t);
@@ -2899,10 +2921,11 @@ void launch_camera_rays(igx_device* dev, int grid, const FrameArgs& fa, const Sc
 #endif
 
 #if IGX_PART == 0
-// k_generate on dev->stream, with the camera models of the scene's shading variant
-void launch_generate(igx_device* dev, int grid, const FrameArgs& fa, const PathBuf& out, float4* L, int* cnt0) {
-    if (dev->full_shading) hipLaunchKernelGGL(k_generate_full, dim3(grid), dim3(BLOCK), 0, dev->stream, fa, dev->sv, out, L, cnt0);
-    else hipLaunchKernelGGL(k_generate, dim3(grid), dim3(BLOCK), 0, dev->stream, fa, dev->sv, out, L, cnt0);
+// k_generate on the main stream, with the camera models of the scene's shading variant
+void launch_generate(igx_device* dev, const LaunchCtx& ctx, int grid, const FrameArgs& fa, const PathBuf& out, float4* L, int* cnt0) {
+    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
+    if (dev->full_shading) hipLaunchKernelGGL(k_generate_full, dim3(grid), dim3(BLOCK), 0, ctx.main, fa, sv, out, L, cnt0);
+    else hipLaunchKernelGGL(k_generate, dim3(grid), dim3(BLOCK), 0, ctx.main, fa, sv, out, L, cnt0);
 }
 
 // Wait for the chunk last run in `s` and fold its statistics in.
@@ -3040,34 +3063,6 @@ void configure_treelet(igx_device* dev) {
     // k_trace_refill and the tail kernels: none -- the tail kernel overlaps the
     // next chunk's kernels, and LDS it holds keeps their blocks off the CU
     // (soup-1M frame +4 % with one)
-}
-
-// Film pixels among the chunk's local pixels (tiles at the film's right and
-// bottom edges hang over it): per tile in closed form, the valid pixels among
-// a tile's first m row-major pixels being min(m / T, h) * w + (m / T < h ?
-// min(m % T, w) : 0).  (A per-pixel loop cost 8 ms of host time per 67 M-path
-// config-5 chunk, during which the GPU idled: profiles/r04_timeline_gaps.log.)
-long long valid_pixels_in_chunk(const FrameArgs& fa) {
-    if (fa.num_rays > 0 || fa.tile_size <= 0) return fa.chunk_pixels;
-    long long v = 0;
-    const long long T = fa.tile_size, TT = T * T;
-    const long long c0 = fa.chunk_pixel0, c1 = c0 + fa.chunk_pixels;
-    for (long long k = c0 / TT; k * TT < c1; ++k) {
-        const long long t = fa.tile_offset + k * fa.tile_stride;
-        const long long ty = t / fa.tiles_x, tx = t - ty * fa.tiles_x;
-        const long long w = std::max(0ll, std::min(T, fa.width - tx * T)), h = std::max(0ll, std::min(T, fa.height - ty * T));
-        auto valid_first = [&](long long m) { // valid pixels among the tile's first m
-            if (IGX_PIXEL_BLOCKS && (T & 3) == 0) { // 4 x 2 blocks along row pairs (block_order)
-                const long long pairs = m / (2 * T), q = m - pairs * 2 * T, nb = q / 8, rem = q - nb * 8;
-                const long long y0 = 2 * pairs, c0 = 4 * nb + std::min(rem, 4ll), c1 = 4 * nb + std::max(0ll, rem - 4);
-                return std::min(y0, h) * w + (y0 < h ? std::min(c0, w) : 0) + (y0 + 1 < h ? std::min(c1, w) : 0);
-            }
-            const long long rows = m / T;
-            return std::min(rows, h) * w + (rows < h ? std::min(m % T, w) : 0);
-        };
-        v += valid_first(std::min(TT, c1 - k * TT)) - valid_first(std::max(0ll, c0 - k * TT));
-    }
-    return v;
 }
 
 CameraModel make_camera(const igx_device* dev, int width, int height) {
@@ -3417,15 +3412,21 @@ extern "C" igx_status igx_upload_scene(igx_device* dev, const igx_scene_desc* de
 // last chunk of frame k overlaps the first of frame k + 1 too (one chunk per
 // frame on an 8-rank diamond share).  Every other call waits until the queue
 // has drained (wait_idle).
-struct ChunkPlan { // one render call's chunking (render_impl)
-    FrameArgs fa{};
+struct ChunkPlan { // one render call: its chunking (host/render_plan.h) and what each of its chunks launches with
+    RenderPlan rp;
+    FrameArgs fa{}; // the call's; begin_chunk fills in the chunk's own fields
     CameraModel cam{};
-    int iteration = 0, spi = 1, count = 1, width = 1;
-    long long local_pixels = 0, chunk_pixels_max = 0;
-    int iters_per_chunk = 1;
-    size_t slot_cap = 0;
-    int max_bounces = 1, ext_bpc = 1, sh_bpc = 1, fin_bpc = 1;
+    int iteration = 0; // the call's first iteration
+    bool split = false, aov = false, full = false; // k_trace + k_shade; the MIS AOV slots; the full shading variant
+    int max_bounces = 1, ext_bpc = 1, tr_bpc = 1, shade_bpc = 1, sh_bpc = 1, fin_bpc = 1;
     bool pairs = false;
+};
+struct ChunkRun { // one chunk from begin_chunk to queue_resolve
+    FrameArgs fa{};
+    long long n = 0; // paths
+    int tail = 0, fin_grid = 0;
+    bool fuse_gen = false;
+    hipEvent_t sh_done = nullptr; // the last shadow launch on a shadow stream of its own
 };
 // One info-buffer pass (k_infobuffer): the iterations of one render call
 struct InfoPass {
@@ -3445,15 +3446,10 @@ struct SchedItem {
     std::shared_ptr<const InfoPass> info;
     bool fence() const { return clear || info; } // no chunk of its own
     std::shared_ptr<const ChunkPlan> plan;
-    int it0 = 0;
-    long long px0 = 0;
-    bool last_of_plan = false;
+    Chunk c;
     bool started = false;
     int slot = 0;
-    FrameArgs fa{};
-    long long n = 0;
-    int tail = 0, chunk_pixels = 0, ext_grid = 0, sh_grid = 0, fin_grid = 0;
-    bool fuse_gen = false;
+    ChunkRun run;
     int b = 0, switch_b = -1;
     long long live = 0; // paths entering the last bounce whose count arrived
     bool loop_done = false, tail_queued = false;
@@ -3463,17 +3459,12 @@ struct ChunkScheduler {
     std::deque<SchedItem> items; // submission order
     bool empty() const { return items.empty(); }
     void add(const std::shared_ptr<const ChunkPlan>& plan) {
-        const ChunkPlan& pl = *plan;
-        const size_t first = items.size();
-        for (int it0 = 0; it0 < pl.count; it0 += pl.iters_per_chunk)
-            for (long long px0 = 0; px0 < pl.local_pixels; px0 += pl.chunk_pixels_max) {
-                SchedItem s;
-                s.plan = plan;
-                s.it0 = it0;
-                s.px0 = px0;
-                items.push_back(s);
-            }
-        if (items.size() > first) items.back().last_of_plan = true;
+        for (long long k = 0, chunks = chunk_count(plan->rp); k < chunks; ++k) {
+            SchedItem s;
+            s.plan = plan;
+            s.c = plan_chunk(plan->rp, k);
+            items.push_back(s);
+        }
     }
     void add_clear(uint32_t mask) {
         SchedItem s;
@@ -3492,7 +3483,7 @@ struct ChunkScheduler {
         for (const SchedItem& r : items) {
             if (r.fence()) continue;
             if (!r.started) return false;
-            if (!r.loop_done && r.live * 100 > (long long)pct * r.n) return false;
+            if (!r.loop_done && r.live * 100 > (long long)pct * r.c.n) return false;
         }
         return true;
     }
@@ -3550,45 +3541,180 @@ static igx_status queue_info_pass(igx_device* dev, const InfoPass& ps, hipStream
     return IGX_OK;
 }
 
-igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
-    hipStream_t const main0 = dev->stream, tail0 = dev->tail_stream;
-    int* const spill0 = dev->spill_main;
-    int* const spill_tail0 = dev->spill_tail;
-    hipStream_t const slot_stream[2] = {dev->stream, dev->stream2};
-    int* const slot_spill[2] = {dev->spill_main, dev->spill_main2};
+// ---------------------------------------------------------------------------
+// The steps of one chunk, shared by the sequential schedule (render_impl) and
+// the concurrent one (ChunkScheduler::step).  Each queues its work on the
+// streams of `ctx` and waits for nothing but the slot's previous chunk
+// (begin_chunk); when the host waits for counts is the schedules' business.
+// ---------------------------------------------------------------------------
+// option "timing": an event pair around the launches between the two calls
+static void begin_timed(igx_device* dev, Slot& S, int kind, int bounce, hipStream_t strm) {
+    if (!dev->timing) return;
+    TimedLaunch t{slot_event(S), slot_event(S), kind, bounce};
+    (void)hipEventRecord(t.a, strm);
+    S.timed.push_back(t);
+}
+static void end_timed(igx_device* dev, Slot& S, hipStream_t strm) {
+    if (!dev->timing) return;
+    (void)hipEventRecord(S.timed.back().b, strm);
+}
+// counter row r of the slot: row 2b = paths entering bounce b, row 2b+1 = shadow rays of bounce b
+static int* ctr_row(const Slot& S, int r) { return S.ctr + (size_t)r * CROW; }
+
+// Chunk `c` of the plan moves into slot S: waits for (and harvests) the chunk
+// that last ran there, sizes the slot, fills in the chunk's FrameArgs and
+// tail threshold, zeroes the counter rows and generates the camera paths
+// unless bounce 0 of the fused k_extend will.
+static igx_status begin_chunk(igx_device* dev, const LaunchCtx& ctx, Slot& S, const ChunkPlan& pl, const Chunk& c, ChunkRun& r) {
+    igx_status st = harvest(dev, S);
+    if (st != IGX_OK || (st = ensure_slot(dev, S, pl.rp.slot_cap, pl.split, pl.fa.classify >= 4, pl.aov)) != IGX_OK) return st;
+    r = ChunkRun{};
+    r.fa = pl.fa;
+    // the slot keeps AOV buffers from an earlier aov_mis scene: only a scene
+    // with the AOVs (and their films) writes them
+    r.fa.aov_di = pl.aov && dev->aov_fb[0] ? S.aov_di : nullptr;
+    r.fa.aov_nee = pl.aov && dev->aov_fb[1] ? S.aov_nee : nullptr;
+    S.sh.aov_nee = r.fa.aov_nee;
+    S.sh.optimistic = r.fa.shadow_optimistic;
+    r.fa.iter = pl.iteration + c.it0;
+    r.fa.chunk_iters = c.chunk_iters;
+    r.fa.chunk_pixel0 = (int)c.px0;
+    r.fa.chunk_pixels = c.chunk_pixels;
+    r.n = c.n;
+    // paths one pass of the tail kernel holds (lane pairs: one path per two lanes)
+    const long long fin_lanes = (long long)pl.fin_bpc * dev->num_cus * BLOCK / (pl.pairs ? 2 : 1);
+    r.tail = tail_threshold(r.n, fin_lanes, dev->tail_opt, dev->tail_last_opt, c.last);
+    S.tail = r.tail;
+    const FrameArgs& fa = r.fa;
+    const TileShare share{fa.width, fa.height, fa.num_rays, fa.tile_size, fa.tile_offset, fa.tile_stride, fa.tiles_x};
+    S.camera = valid_pixels_in_chunk(share, fa.chunk_pixel0, fa.chunk_pixels) * pl.rp.spi * fa.chunk_iters;
+    S.n0 = r.n;
+    S.split = pl.split;
+    S.bounce_ev.clear();
+    S.launched = 0;
+    r.fin_grid = grid_for(dev, std::min<long long>(r.n, r.tail) * (pl.pairs ? 2 : 1), pl.fin_bpc);
+    // camera paths: built by bounce 0 of the fused k_extend when the chunk
+    // runs through it (saves the 72 B/path round trip of k_generate)
+    r.fuse_gen = dev->fuse_generate && !pl.split && r.n > r.tail;
+    HIPCHK(hipMemsetAsync(S.ctr, 0, (size_t)(2 * pl.max_bounces + 4) * CROW * sizeof(int), ctx.main));
+    if (dev->dynamic_opt)
+        HIPCHK(hipMemsetAsync(S.ctr + (size_t)WORK_ROW0 * CROW, 0, (size_t)4 * pl.max_bounces * CROW * sizeof(int), ctx.main));
+    if (!r.fuse_gen) {
+        begin_timed(dev, S, 2, -1, ctx.main);
+        launch_generate(dev, ctx, grid_for(dev, r.n, 8), r.fa, S.pa, S.L, S.ctr);
+        end_timed(dev, S, ctx.main);
+        HIPCHK(hipGetLastError());
+    }
+    return IGX_OK;
+}
+
+// Bounce b of the chunk: the fused k_extend, or k_trace + k_shade, then the
+// shadow kernel, the copy of the bounce's counts to the host mirror and the
+// event behind it (S.bounce_ev[b]).  `bound`: the paths known to remain (the
+// count entering bounce b - 1 once it has arrived, an upper bound for bounce
+// b's paths and shadow rays): late bounces launch few waves, not a full chip
+// of waves that find no group (IGX_LIVE_GRID).
+// Split schedule with a shadow stream of its own (ctx.shadow): the shadow rays
+// of bounce b overlap the trace of bounce b + 1 (independent: both come from
+// shade(b)); shade(b + 1) waits for them, as both add to the radiance slots,
+// so the additions keep their order and the image is unchanged.
+static igx_status queue_bounce(igx_device* dev, const LaunchCtx& ctx, Slot& S, const ChunkPlan& pl, ChunkRun& r, int b, long long bound) {
     const bool inst = dev->instrument;
-    // the launch helpers read dev->stream, dev->tail_stream, dev->sv (camera,
-    // spill columns): point them at slot k and the item's camera while its
-    // work is queued
-    auto use_slot = [&](const SchedItem& r) {
-        dev->stream = dev->tail_stream = slot_stream[r.slot];
-        dev->sv.spill = dev->spill_tail = slot_spill[r.slot];
-        set_camera(dev->sv, r.plan->cam);
+    const bool overlap = ctx.shadow != ctx.main;
+    const int sh_grid = grid_for(dev, bound, pl.sh_bpc);
+    PathBuf in = (b & 1) ? S.pb : S.pa, out = (b & 1) ? S.pa : S.pb;
+    KernelCounters kc{ctr_row(S, 2 * b), ctr_row(S, 2 * (b + 1)), ctr_row(S, 2 * b + 1), dev->dstats, ctr_row(S, WORK_ROW0 + 4 * b)};
+    if (pl.split) {
+        const int tr_grid = grid_for(dev, bound, pl.tr_bpc), shade_grid = grid_for(dev, bound, pl.shade_bpc);
+        begin_timed(dev, S, 5, b, ctx.main);
+        int* const tr_work = (dev->dynamic_opt & DYN_REFILL_TRACE) ? ctr_row(S, WORK_ROW0 + 4 * b) : nullptr;
+        if (inst) launch_trace<true>(dev, ctx, S, tr_grid, r.fa, in, ctr_row(S, 2 * b), r.tail, tr_work);
+        else launch_trace<false>(dev, ctx, S, tr_grid, r.fa, in, ctr_row(S, 2 * b), r.tail, tr_work);
+        end_timed(dev, S, ctx.main);
+        if (r.sh_done) HIPCHK(hipStreamWaitEvent(ctx.main, r.sh_done, 0));
+        begin_timed(dev, S, 0, b, ctx.main);
+        launch_shade(dev, ctx, pl.full, shade_grid, r.fa, in, S.hb, out, S.sh, S.L, kc, r.tail);
+        end_timed(dev, S, ctx.main);
+    } else {
+        const int ext_grid = grid_for(dev, bound, pl.ext_bpc, dev->ext_block);
+        begin_timed(dev, S, 0, b, ctx.main);
+        FrameArgs fb = r.fa;
+        fb.gen_n = r.fuse_gen && b == 0 ? (int)r.n : 0;
+        if (inst) launch_extend<true>(dev, ctx, S, ext_grid, fb, in, out, kc, r.tail);
+        else launch_extend<false>(dev, ctx, S, ext_grid, fb, in, out, kc, r.tail);
+        end_timed(dev, S, ctx.main);
+    }
+    if (overlap) {
+        hipEvent_t shaded = slot_event(S);
+        HIPCHK(hipEventRecord(shaded, ctx.main));
+        HIPCHK(hipStreamWaitEvent(ctx.shadow, shaded, 0));
+    }
+    begin_timed(dev, S, 1, b, ctx.shadow);
+    int* const sh_work =
+        (dev->dynamic_opt & (use_refill(dev) ? DYN_REFILL_SHADOW : DYN_SHADOW)) ? ctr_row(S, WORK_ROW0 + 4 * b + 2) : nullptr;
+    if (inst) launch_shadow<true>(dev, ctx, S, sh_grid, ctr_row(S, 2 * b + 1), sh_work);
+    else launch_shadow<false>(dev, ctx, S, sh_grid, ctr_row(S, 2 * b + 1), sh_work);
+    end_timed(dev, S, ctx.shadow);
+    if (overlap) {
+        r.sh_done = slot_event(S);
+        HIPCHK(hipEventRecord(r.sh_done, ctx.shadow));
+    }
+    HIPCHK(hipGetLastError());
+    // shadow counts of bounce b and path counts entering bounce b+1 (adjacent rows)
+    HIPCHK(hipMemcpyAsync(S.pinned + (size_t)(2 * b + 1) * CROW, ctr_row(S, 2 * b + 1), 2 * CROW * sizeof(int), hipMemcpyDeviceToHost,
+                          ctx.main));
+    hipEvent_t e = slot_event(S);
+    HIPCHK(hipEventRecord(e, ctx.main));
+    S.bounce_ev.push_back(e);
+    ++S.launched;
+    return IGX_OK;
+}
+
+// Every bounce is queued and its counts have arrived: the first bounce whose
+// paths are at or below the tail threshold
+static int find_switch_bounce(const Slot& S, int max_bounces, int tail) {
+    for (int b = 1; b <= max_bounces; ++b)
+        if (row_total(S, 2 * b) <= tail) return b;
+    return max_bounces;
+}
+
+// The tail kernel takes the paths entering bounce switch_b to their end (ctx.tail)
+static igx_status queue_tail(igx_device* dev, const LaunchCtx& ctx, Slot& S, const ChunkRun& r, int switch_b) {
+    S.switch_bounce = switch_b;
+    if (switch_b >= MAX_BOUNCES) return IGX_OK;
+    PathBuf in = (switch_b & 1) ? S.pb : S.pa;
+    begin_timed(dev, S, 4, switch_b, ctx.tail);
+    if (dev->instrument) launch_finish<true>(dev, ctx, S, r.fin_grid, r.fa, in, ctr_row(S, 2 * switch_b), r.tail);
+    else launch_finish<false>(dev, ctx, S, r.fin_grid, r.fa, in, ctr_row(S, 2 * switch_b), r.tail);
+    end_timed(dev, S, ctx.tail);
+    HIPCHK(hipGetLastError());
+    return IGX_OK;
+}
+
+// The chunk's radiance slots go to the film (and the MIS AOVs', resolved like
+// it, to theirs) on `strm`; S.done marks the slot free again
+static igx_status queue_resolve(igx_device* dev, Slot& S, const ChunkRun& r, int fb_width, hipStream_t strm) {
+    const dim3 grid((r.fa.chunk_pixels + 63) / 64), block(64 * RES_G);
+    begin_timed(dev, S, 3, -1, strm);
+    hipLaunchKernelGGL(k_resolve, grid, block, 0, strm, r.fa, S.L, dev->fb, fb_width);
+    if (r.fa.aov_di)
+        for (int k = 0; k < 2; ++k) hipLaunchKernelGGL(k_resolve, grid, block, 0, strm, r.fa, k ? S.aov_nee : S.aov_di, dev->aov_fb[k], fb_width);
+    end_timed(dev, S, strm);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.done, strm));
+    S.pending = true;
+    return IGX_OK;
+}
+
+igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
+    // slot k's chunk runs on a stream of its own, tail kernel included, with
+    // that stream's spill columns (the fused schedule: no shadow stream)
+    const auto slot_ctx = [&](const SchedItem& r) {
+        hipStream_t const strm = r.slot ? dev->stream2 : dev->stream;
+        int* const spill = r.slot ? dev->spill_main2 : dev->spill_main;
+        return LaunchCtx{strm, strm, strm, spill, spill, spill, r.plan->cam};
     };
-    auto restore = [&]() {
-        dev->stream = main0;
-        dev->tail_stream = tail0;
-        dev->sv.spill = spill0;
-        dev->spill_tail = spill_tail0;
-    };
-    auto begin_timed = [&](Slot& S, int kind, int bounce, hipStream_t strm) {
-        if (!dev->timing) return;
-        TimedLaunch t{slot_event(S), slot_event(S), kind, bounce};
-        (void)hipEventRecord(t.a, strm);
-        S.timed.push_back(t);
-    };
-    auto end_timed = [&](Slot& S, hipStream_t strm) {
-        if (!dev->timing) return;
-        (void)hipEventRecord(S.timed.back().b, strm);
-    };
-#define IGX_CC(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            restore();                                                                                 \
-            return fail(dev, IGX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));         \
-        }                                                                                              \
-    } while (0)
+    igx_status st;
     // start the next chunk once its slot's previous chunk has resolved and
     // every running chunk is in its late bounces (live paths at most
     // concurrent_start_pct % of its own): two chunks started together only
@@ -3601,7 +3727,7 @@ igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
             nx = &r;
             break;
         }
-        if (!r.loop_done && r.live * 100 > (long long)dev->concurrent_start_pct * r.n) late = false;
+        if (!r.loop_done && r.live * 100 > (long long)dev->concurrent_start_pct * r.c.n) late = false;
     }
     if (nx && late) {
         const int k = dev->stream_slots == 1 ? 0 : dev->next_slot;
@@ -3611,63 +3737,18 @@ igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
         if (!busy && S.pending) {
             const hipError_t q = hipEventQuery(S.done);
             if (q == hipErrorNotReady) busy = true;
-            else IGX_CC(q);
+            else HIPCHK(q);
         }
         if (!busy) {
             SchedItem& r = *nx;
-            const ChunkPlan& pl = *r.plan;
-            if (dev->fail_chunk_opt > 0 && --dev->fail_chunk_opt == 0) { // test hook (option "fail_chunk")
-                restore();
+            if (dev->fail_chunk_opt > 0 && --dev->fail_chunk_opt == 0) // test hook (option "fail_chunk")
                 return fail(dev, IGX_ERR_HIP, "injected failure (option fail_chunk)");
-            }
-            igx_status st;
-            if ((st = harvest(dev, S)) != IGX_OK || (st = ensure_slot(dev, S, pl.slot_cap, false, pl.fa.classify >= 4, dev->aov_on)) != IGX_OK) {
-                restore();
-                return st;
-            }
+            r.slot = k;
+            if ((st = begin_chunk(dev, slot_ctx(r), S, *r.plan, r.c, r.run)) != IGX_OK) return st;
             if (dev->stream_slots == 2) dev->next_slot ^= 1;
             r.started = true;
-            r.slot = k;
-            r.fa = pl.fa;
-            // the slot keeps AOV buffers from an earlier aov_mis scene: only
-            // a scene with the AOVs (and their films) writes them
-            r.fa.aov_di = dev->aov_on && dev->aov_fb[0] ? S.aov_di : nullptr;
-            r.fa.aov_nee = dev->aov_on && dev->aov_fb[1] ? S.aov_nee : nullptr;
-            S.sh.aov_nee = r.fa.aov_nee;
-            S.sh.optimistic = r.fa.shadow_optimistic;
-            r.fa.iter = pl.iteration + r.it0;
-            r.fa.chunk_iters = std::min(pl.iters_per_chunk, pl.count - r.it0);
-            r.chunk_pixels = (int)std::min<long long>(pl.chunk_pixels_max, pl.local_pixels - r.px0);
-            r.fa.chunk_pixel0 = (int)r.px0;
-            r.fa.chunk_pixels = r.chunk_pixels;
-            r.n = (long long)r.chunk_pixels * pl.spi * r.fa.chunk_iters;
-            r.live = r.n;
-            // tail threshold: as the sequential schedule (render_impl)
-            const long long fin_lanes = (long long)pl.fin_bpc * dev->num_cus * BLOCK / (pl.pairs ? 2 : 1);
-            const int64_t topt = r.last_of_plan && dev->tail_last_opt >= 0 ? dev->tail_last_opt : dev->tail_opt;
-            r.tail = topt >= 0 ? (int)std::min<int64_t>(topt, 1 << 30) : (int)std::max<long long>(32768, std::min(r.n / 64, fin_lanes));
-            S.tail = r.tail;
-            S.camera = valid_pixels_in_chunk(r.fa) * pl.spi * r.fa.chunk_iters;
-            S.n0 = r.n;
-            S.split = false;
-            S.bounce_ev.clear();
-            S.launched = 0;
-            r.ext_grid = grid_for(dev, r.n, pl.ext_bpc, dev->ext_block);
-            r.sh_grid = grid_for(dev, r.n, pl.sh_bpc);
-            r.fin_grid = grid_for(dev, std::min<long long>(r.n, r.tail) * (pl.pairs ? 2 : 1), pl.fin_bpc);
-            r.fuse_gen = dev->fuse_generate && r.n > r.tail;
-            use_slot(r);
-            IGX_CC(hipMemsetAsync(S.ctr, 0, (size_t)(2 * pl.max_bounces + 4) * CROW * sizeof(int), dev->stream));
-            if (dev->dynamic_opt)
-                IGX_CC(hipMemsetAsync(S.ctr + (size_t)WORK_ROW0 * CROW, 0, (size_t)4 * pl.max_bounces * CROW * sizeof(int), dev->stream));
-            if (!r.fuse_gen) {
-                begin_timed(S, 2, -1, dev->stream);
-                launch_generate(dev, grid_for(dev, r.n, 8), r.fa, S.pa, S.L, S.ctr);
-                end_timed(S, dev->stream);
-                IGX_CC(hipGetLastError());
-            }
-            restore();
-            if (r.n <= r.tail) { // the whole chunk is one tail pass
+            r.live = r.run.n;
+            if (r.run.n <= r.run.tail) { // the whole chunk is one tail pass
                 r.switch_b = 0;
                 r.loop_done = true;
             }
@@ -3679,110 +3760,53 @@ igx_status ChunkScheduler::step(igx_device* dev, bool& progress) {
         if (r.fence() || !r.started || r.tail_queued) continue;
         Slot& S = dev->slots[r.slot];
         const ChunkPlan& pl = *r.plan;
-        const int max_bounces = pl.max_bounces;
-        int* const cnt = S.ctr;
-        auto row = [&](int rr) { return cnt + (size_t)rr * CROW; };
-        use_slot(r);
+        const LaunchCtx ctx = slot_ctx(r);
         while (!r.loop_done) {
-            if (r.b < max_bounces) {
-                if (r.b >= 2) {
-                    const hipError_t q = hipEventQuery(S.bounce_ev[r.b - 2]);
-                    if (q == hipErrorNotReady) break;
-                    IGX_CC(q);
-                    r.live = row_total(S, 2 * (r.b - 1));
-                    if (r.live <= r.tail) {
-                        r.switch_b = r.b - 1;
-                        r.loop_done = true;
-                        break;
-                    }
-                }
-                const int b = r.b;
-                PathBuf in = (b & 1) ? S.pb : S.pa, out = (b & 1) ? S.pa : S.pb;
-                KernelCounters kc{row(2 * b), row(2 * (b + 1)), row(2 * b + 1), dev->dstats, row(WORK_ROW0 + 4 * b)};
-                begin_timed(S, 0, b, dev->stream);
-                FrameArgs fb = r.fa;
-                fb.gen_n = r.fuse_gen && b == 0 ? (int)r.n : 0;
-                // grids sized to the paths known to remain (r.live: the count
-                // entering bounce b - 1, an upper bound for bounce b's paths and
-                // shadow rays): late bounces launch few waves, not a full chip
-                // of waves that find no group (IGX_LIVE_GRID)
-                const long long bound = IGX_LIVE_GRID && b >= 2 ? r.live : r.n;
-                const int ext_grid = IGX_LIVE_GRID ? grid_for(dev, bound, pl.ext_bpc, dev->ext_block) : r.ext_grid;
-                const int sh_grid = IGX_LIVE_GRID ? grid_for(dev, bound, pl.sh_bpc) : r.sh_grid;
-                if (inst) launch_extend<true>(dev, S, ext_grid, fb, in, out, kc, r.tail);
-                else launch_extend<false>(dev, S, ext_grid, fb, in, out, kc, r.tail);
-                end_timed(S, dev->stream);
-                begin_timed(S, 1, b, dev->stream);
-                int* const sh_work =
-                    (dev->dynamic_opt & (use_refill(dev) ? DYN_REFILL_SHADOW : DYN_SHADOW)) ? row(WORK_ROW0 + 4 * b + 2) : nullptr;
-                if (inst) launch_shadow<true>(dev, S, sh_grid, row(2 * b + 1), sh_work, dev->stream);
-                else launch_shadow<false>(dev, S, sh_grid, row(2 * b + 1), sh_work, dev->stream);
-                end_timed(S, dev->stream);
-                IGX_CC(hipGetLastError());
-                IGX_CC(hipMemcpyAsync(S.pinned + (size_t)(2 * b + 1) * CROW, row(2 * b + 1), 2 * CROW * sizeof(int),
-                                      hipMemcpyDeviceToHost, dev->stream));
-                hipEvent_t e = slot_event(S);
-                IGX_CC(hipEventRecord(e, dev->stream));
-                S.bounce_ev.push_back(e);
-                ++S.launched;
-                ++r.b;
-                progress = true;
-            } else {
+            if (r.b >= pl.max_bounces) {
                 // every bounce queued: the counts are known once the last one completed
                 const hipError_t q = hipEventQuery(S.bounce_ev.back());
                 if (q == hipErrorNotReady) break;
-                IGX_CC(q);
-                r.switch_b = max_bounces;
-                for (int b = 1; b <= max_bounces; ++b)
-                    if (row_total(S, 2 * b) <= r.tail) {
-                        r.switch_b = b;
-                        break;
-                    }
+                HIPCHK(q);
+                r.switch_b = find_switch_bounce(S, pl.max_bounces, r.run.tail);
                 r.loop_done = true;
+                break;
             }
+            if (r.b >= 2) {
+                const hipError_t q = hipEventQuery(S.bounce_ev[r.b - 2]);
+                if (q == hipErrorNotReady) break;
+                HIPCHK(q);
+                r.live = row_total(S, 2 * (r.b - 1));
+                if (r.live <= r.run.tail) {
+                    r.switch_b = r.b - 1;
+                    r.loop_done = true;
+                    break;
+                }
+            }
+            if ((st = queue_bounce(dev, ctx, S, pl, r.run, r.b, IGX_LIVE_GRID && r.b >= 2 ? r.live : r.run.n)) != IGX_OK) return st;
+            ++r.b;
+            progress = true;
         }
-        if (r.loop_done && !r.tail_queued) {
-            S.switch_bounce = r.switch_b;
-            if (r.switch_b < MAX_BOUNCES) {
-                PathBuf in = (r.switch_b & 1) ? S.pb : S.pa;
-                begin_timed(S, 4, r.switch_b, dev->stream);
-                if (inst) launch_finish<true>(dev, S, r.fin_grid, r.fa, in, row(2 * r.switch_b), r.tail);
-                else launch_finish<false>(dev, S, r.fin_grid, r.fa, in, row(2 * r.switch_b), r.tail);
-                end_timed(S, dev->stream);
-                IGX_CC(hipGetLastError());
-            }
+        if (r.loop_done) {
+            if ((st = queue_tail(dev, ctx, S, r.run, r.switch_b)) != IGX_OK) return st;
             r.fin_ev = slot_event(S);
-            IGX_CC(hipEventRecord(r.fin_ev, dev->stream));
+            HIPCHK(hipEventRecord(r.fin_ev, ctx.main));
             r.tail_queued = true;
             progress = true;
         }
-        restore();
     }
     // resolves, framebuffer clears and info-buffer passes strictly in submission order on the tail stream
     while (!items.empty() && (items.front().fence() || items.front().tail_queued)) {
         SchedItem& r = items.front();
-        if (r.fence()) {
-            const igx_status st = r.clear ? queue_clear(dev, r.clear_mask, tail0) : queue_info_pass(dev, *r.info, tail0, spill_tail0);
-            if (st != IGX_OK) return st;
-        } else {
-            Slot& S = dev->slots[r.slot];
-            IGX_CC(hipStreamWaitEvent(tail0, r.fin_ev, 0));
-            begin_timed(S, 3, -1, tail0);
-            hipLaunchKernelGGL(k_resolve, dim3((r.chunk_pixels + 63) / 64), dim3(64 * RES_G), 0, tail0, r.fa, S.L, dev->fb, r.plan->width);
-            if (r.fa.aov_di) // the MIS AOVs, resolved like the film
-                for (int k = 0; k < 2; ++k)
-                    hipLaunchKernelGGL(k_resolve, dim3((r.chunk_pixels + 63) / 64), dim3(64 * RES_G), 0, tail0, r.fa,
-                                       k ? S.aov_nee : S.aov_di, dev->aov_fb[k], r.plan->width);
-            end_timed(S, tail0);
-            IGX_CC(hipGetLastError());
-            IGX_CC(hipEventRecord(S.done, tail0));
-            S.pending = true;
+        if (r.clear) st = queue_clear(dev, r.clear_mask, dev->tail_stream);
+        else if (r.info) st = queue_info_pass(dev, *r.info, dev->tail_stream, dev->spill_tail);
+        else {
+            HIPCHK(hipStreamWaitEvent(dev->tail_stream, r.fin_ev, 0));
+            st = queue_resolve(dev, dev->slots[r.slot], r.run, r.plan->rp.width, dev->tail_stream);
         }
+        if (st != IGX_OK) return st;
         items.pop_front();
         progress = true;
     }
-#undef IGX_CC
-    restore();
     return IGX_OK;
 }
 
@@ -3943,22 +3967,23 @@ static void submit_async(igx_device* dev, AsyncRender::Job job) {
 static igx_status render_impl(igx_device* dev, const igx_render_params* p, int count) {
     if (!dev || !p || count < 1) return IGX_ERR_INVALID_ARGUMENT;
     if (!dev->has_scene) return fail(dev, IGX_ERR_NO_SCENE, "no scene uploaded");
-    if (p->spi < 1) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "spi must be >= 1");
     auto t_start = std::chrono::steady_clock::now();
-    HIPCHK(hipSetDevice(dev->hip_device));
-    const bool list_mode = p->num_rays > 0;
-    int width = list_mode ? p->num_rays : p->width;
-    int height = list_mode ? 1 : p->height;
-    if (width < 1 || height < 1) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "film size must be positive");
-    if (p->tile_size > 0 && (p->tile_stride < 1 || p->tile_offset < 0 || p->tile_offset >= p->tile_stride))
-        return fail(dev, IGX_ERR_INVALID_ARGUMENT, "invalid tile sharding parameters");
-    if (list_mode && p->tile_size > 0) return fail(dev, IGX_ERR_INVALID_ARGUMENT, "ray-list mode cannot be tile-sharded");
     // schedule: concurrent chunks on the fused schedule with two slots, queued
     // for the handle's worker thread when async_render is on; anything else
     // runs here once the worker has drained
+    const bool list_mode = p->num_rays > 0;
     const bool split = use_split(dev);
     const bool conc = !list_mode && !split && dev->concurrent_opt;
     const bool async = conc && dev->async_opt;
+    const bool want_aov = dev->aov_on && !list_mode;
+    // the call's share of the film and its chunking (host/render_plan.h)
+    ChunkPlan plan;
+    const RenderPlan& rp = plan.rp = plan_render(RenderPlanInput{
+        p->width, p->height, p->num_rays, p->tile_size, p->tile_offset, p->tile_stride, p->spi, count, dev->capacity_opt,
+        dev->slot_budget_mb, dev->stream_slots, dev->mem_total, dev->classify_opt, split, want_aov});
+    if (rp.status != IGX_OK) return fail(dev, rp.status, rp.error);
+    HIPCHK(hipSetDevice(dev->hip_device));
+    const int width = rp.width, height = rp.height;
     if (!async) {
         igx_status w = wait_idle(dev);
         if (w != IGX_OK) return w;
@@ -3972,7 +3997,6 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
 
     // framebuffer (resize clears, as Device::resize)
     size_t fbc = (size_t)width * height * 3;
-    const bool want_aov = dev->aov_on && !list_mode;
     const bool resize = dev->fb_w != width || dev->fb_h != height || !dev->fb || want_aov != (dev->aov_fb[0] != nullptr);
     // the denoiser's three films come and go with option "denoise_aovs"; a
     // resize clears them (and their counts) with the film
@@ -4017,10 +4041,9 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
         dev->rays_frame = p->frame;
         dev->rays_seed = p->seed;
     }
-    const CameraModel cam = make_camera(dev, width, height);
-    if (!async) set_camera(dev->sv, cam); // the worker sets each chunk's camera itself
+    const CameraModel cam = plan.cam = make_camera(dev, width, height);
 
-    FrameArgs fa{};
+    FrameArgs& fa = plan.fa;
     fa.width = width;
     fa.height = height;
     fa.spi = p->spi;
@@ -4030,11 +4053,10 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
     fa.inv_spi = 1.0f / (float)p->spi;
     fa.classify = dev->classify_opt;
     fa.shadow_classes = dev->shadow_classes_opt;
-    fa.shadow_optimistic = use_shadow_optimistic(dev, split, dev->aov_on && !list_mode);
+    fa.shadow_optimistic = use_shadow_optimistic(dev, split, want_aov);
     fa.dynamic = dev->dynamic_opt & DYN_EXTEND;
     fa.reverse = fa.dynamic ? (dev->group_order_opt < 0 ? GROUP_ORDER_AUTO : dev->group_order_opt) : 0;
     fa.probe_sample = dev->probe_sample_opt > 0 && dev->probe_sample_opt <= p->spi ? (int)dev->probe_sample_opt : 0;
-    long long local_pixels;
     if (list_mode) {
         // the previous ray list may still be read by a queued tail kernel
         igx_status dst = drain(dev);
@@ -4048,39 +4070,31 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
         HIPCHK(hipMemcpy(dev->ray_list, p->rays, need * sizeof(float), hipMemcpyHostToDevice));
         fa.num_rays = p->num_rays;
         fa.rays = dev->ray_list;
-        local_pixels = p->num_rays;
     } else if (p->tile_size > 0) {
         fa.tile_size = p->tile_size;
         fa.tile_offset = p->tile_offset;
         fa.tile_stride = p->tile_stride;
-        fa.tiles_x = (width + p->tile_size - 1) / p->tile_size;
-        int tiles_y = (height + p->tile_size - 1) / p->tile_size;
-        int tiles = fa.tiles_x * tiles_y;
-        int mine = tiles > p->tile_offset ? (tiles - p->tile_offset + p->tile_stride - 1) / p->tile_stride : 0;
-        local_pixels = (long long)mine * p->tile_size * p->tile_size;
-    } else {
-        local_pixels = (long long)width * height;
+        fa.tiles_x = rp.tiles_x;
     }
-    // capacity: whole iteration resident when it fits (<= 16M paths), pixel aligned
     // The denoiser's info-buffer pass of the iterations that get one
     // (InfoBufferTechnique.cpp:56-66), ahead of their chunks as the reference
     // injects it: one launch, queued in call order where clears and resolves
     // are (the tail stream; with async_render by the worker, like a clear).
     if (const int64_t passes = info_passes_in(dev->info_mode, p->iteration, count); passes > 0 && dev->info_fb[0]) {
         for (uint64_t& c : dev->info_count) c += (uint64_t)passes;
-        if (local_pixels > 0) {
+        if (rp.local_pixels > 0) {
             auto pass = std::make_shared<InfoPass>();
             pass->fa = fa;
             pass->fa.spi = 1;
             pass->fa.inv_spi = 1.0f;
             pass->fa.probe_sample = 0;
             pass->fa.chunk_pixel0 = 0;
-            pass->fa.chunk_pixels = (int)local_pixels;
+            pass->fa.chunk_pixels = (int)rp.local_pixels;
             pass->fa.chunk_iters = count;
             pass->cam = cam;
             pass->ia = InfoArgs{dev->info_fb[0], dev->info_fb[1], dev->info_fb[2], width,
                                 dev->info_mode,  dev->info_follow_specular ? 1 : 0, dev->info_max_depth};
-            pass->grid = grid_for(dev, local_pixels, MAX_BLOCKS_PER_CU);
+            pass->grid = grid_for(dev, rp.local_pixels, MAX_BLOCKS_PER_CU);
             if (async) {
                 AsyncRender::Job job;
                 job.info = std::move(pass);
@@ -4091,255 +4105,93 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
             }
         }
     }
-    long long total_paths = local_pixels * p->spi;
-    if (total_paths == 0) {
+    if (rp.total_paths == 0) {
         dev->iteration_count += count;
         return IGX_OK;
     }
-    // default chunk of a multi-iteration render: the largest power of two
-    // whose stream slots take at most 30 % of the device memory (MI355X: 128 M
-    // paths; two slots of 22.5 GB, 36.9 GB with three path classes).  Fewer,
-    // larger chunks leave fewer tails that overlap nothing: diamond frame 193
-    // -> 179 ms, S-deep 4096^2 865 -> 823 ms from 32 M to 128 M paths
-    // (tools/sweep_frame.py).  Per path and slot: two path buffers (56 B a
-    // record; twice that with the class-C region), shadow ray 48 B, hit
-    // record 20 B (split schedule), radiance 16 B, and the two MIS AOV slots
-    // (32 B) of an aov_mis scene.
-    if (split && fa.classify >= 4) fa.classify = 3; // hit records have no class-C region
-    const long long path_slot_bytes =
-        2 * 56 * (fa.classify >= 4 ? 2 : 1) + 48 + (split ? 20 : 0) + 16 + (dev->aov_on && !list_mode ? 32 : 0);
-    const long long slot_budget =
-        dev->slot_budget_mb > 0 ? dev->slot_budget_mb * (1ll << 20) : (long long)((double)dev->mem_total * 0.3);
-    long long auto_chunk_paths = 1ll << 24;
-    while (auto_chunk_paths < MAX_CHUNK_PATHS && dev->stream_slots * (2 * auto_chunk_paths) * path_slot_bytes <= slot_budget)
-        auto_chunk_paths *= 2;
-    if (dev->slot_budget_mb > 0) // an explicit budget also bounds the chunk below 16 M paths
-        auto_chunk_paths = std::max<long long>(1ll << 20, std::min<long long>(auto_chunk_paths, slot_budget / (dev->stream_slots * path_slot_bytes)));
-    long long cap = dev->capacity_opt > 0 ? dev->capacity_opt
-                                          : (count > 1 ? auto_chunk_paths : std::min<long long>({total_paths, 1ll << 24, auto_chunk_paths}));
-    cap = std::min<long long>(cap, MAX_CHUNK_PATHS);
-    cap = std::max<long long>(p->spi, (cap / p->spi) * p->spi);
-    const long long chunk_pixels_max = std::min<long long>(cap, total_paths) / p->spi;
-    const int iters_per_chunk = total_paths <= cap ? (int)std::min<long long>(count, cap / total_paths) : 1;
-    const size_t slot_cap = (size_t)(chunk_pixels_max * p->spi * iters_per_chunk);
+    fa.classify = rp.classify; // the split schedule has no class-C region
 
-    const int max_bounces = std::min(std::max(dev->sv.max_depth, 1), MAX_BOUNCES - 1);
+    plan.iteration = p->iteration;
+    plan.split = split;
+    plan.aov = want_aov;
+    plan.max_bounces = std::min(std::max(dev->sv.max_depth, 1), MAX_BOUNCES - 1);
     const bool inst = dev->instrument;
     const int sd = dev->variant;
     const size_t ldsb = dev->lds_scene_bytes;
     if (dev->tree_dirty) configure_treelet(dev);
     const size_t wide_dyn = lds_pad16(ldsb) + dev->lds_shading_bytes;
-    const int ext_bpc = dev->ext_block == BLOCK_WIDE
-                            ? (inst ? extend_wide_blocks_per_cu<true>(sd, wide_dyn) : extend_wide_blocks_per_cu<false>(sd, wide_dyn))
-                            : (inst ? extend_blocks_per_cu<true>(sd, ldsb, tree_bytes(dev, dev->tree_ext))
-                                    : extend_blocks_per_cu<false>(sd, ldsb, tree_bytes(dev, dev->tree_ext)));
+    plan.ext_bpc = dev->ext_block == BLOCK_WIDE
+                       ? (inst ? extend_wide_blocks_per_cu<true>(sd, wide_dyn) : extend_wide_blocks_per_cu<false>(sd, wide_dyn))
+                       : (inst ? extend_blocks_per_cu<true>(sd, ldsb, tree_bytes(dev, dev->tree_ext))
+                               : extend_blocks_per_cu<false>(sd, ldsb, tree_bytes(dev, dev->tree_ext)));
     const bool refill = use_refill(dev);
-    const int tr_bpc = inst ? trace_blocks_per_cu<true>(sd, dev->lds_scene_bytes, refill)
-                            : trace_blocks_per_cu<false>(sd, dev->lds_scene_bytes, refill);
-    const bool full = variant_full(sd);
-    const int shade_bpc = shade_blocks_per_cu(full);
-    const int sh_bpc = inst ? shadow_blocks_per_cu<true>(sd, dev->lds_scene_bytes, refill, tree_bytes(dev, dev->tree_shadow))
-                            : shadow_blocks_per_cu<false>(sd, dev->lds_scene_bytes, refill, tree_bytes(dev, dev->tree_shadow));
-    const bool pairs = use_tail_pairs(dev);
-    const int fin_bpc = inst ? finish_blocks_per_cu<true>(sd, ldsb, 0, pairs) : finish_blocks_per_cu<false>(sd, ldsb, 0, pairs);
+    plan.tr_bpc = inst ? trace_blocks_per_cu<true>(sd, ldsb, refill) : trace_blocks_per_cu<false>(sd, ldsb, refill);
+    plan.full = variant_full(sd);
+    plan.shade_bpc = shade_blocks_per_cu(plan.full);
+    plan.sh_bpc = inst ? shadow_blocks_per_cu<true>(sd, ldsb, refill, tree_bytes(dev, dev->tree_shadow))
+                       : shadow_blocks_per_cu<false>(sd, ldsb, refill, tree_bytes(dev, dev->tree_shadow));
+    plan.pairs = use_tail_pairs(dev);
+    plan.fin_bpc = inst ? finish_blocks_per_cu<true>(sd, ldsb, 0, plan.pairs) : finish_blocks_per_cu<false>(sd, ldsb, 0, plan.pairs);
 
     if (conc) {
-        auto plan = std::make_shared<ChunkPlan>();
-        plan->fa = fa;
-        plan->cam = cam;
-        plan->iteration = p->iteration;
-        plan->spi = p->spi;
-        plan->count = count;
-        plan->width = width;
-        plan->local_pixels = local_pixels;
-        plan->chunk_pixels_max = chunk_pixels_max;
-        plan->iters_per_chunk = iters_per_chunk;
-        plan->slot_cap = slot_cap;
-        plan->max_bounces = max_bounces;
-        plan->ext_bpc = ext_bpc;
-        plan->sh_bpc = sh_bpc;
-        plan->fin_bpc = fin_bpc;
-        plan->pairs = pairs;
         dev->iteration_count += count;
         dev->stats.iterations += count;
+        const auto shared = std::make_shared<const ChunkPlan>(plan);
         if (async) {
             AsyncRender::Job job;
-            job.plan = std::move(plan);
+            job.plan = shared;
             submit_async(dev, std::move(job));
         } else {
             ChunkScheduler sched;
-            sched.add(plan);
+            sched.add(shared);
             igx_status st = run_scheduler(dev, sched);
             if (st != IGX_OK) return st;
         }
-        dev->stats.ms_render += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-        return IGX_OK;
-    }
-
-    for (int it0 = 0; it0 < count; it0 += iters_per_chunk)
-    for (long long px0 = 0; px0 < local_pixels; px0 += chunk_pixels_max) {
-        fa.iter = p->iteration + it0;
-        fa.chunk_iters = std::min(iters_per_chunk, count - it0);
-        Slot& S = dev->slots[dev->stream_slots == 1 ? 0 : dev->next_slot];
-        dev->next_slot ^= 1;
-        igx_status st = harvest(dev, S); // waits for the chunk that used this slot two chunks ago (one, with one slot)
-        if (st != IGX_OK) return st;
-        if ((st = ensure_slot(dev, S, slot_cap, split, fa.classify >= 4, dev->aov_on && !list_mode)) != IGX_OK) return st;
-        fa.aov_di = dev->aov_on && dev->aov_fb[0] && !list_mode ? S.aov_di : nullptr;
-        fa.aov_nee = dev->aov_on && dev->aov_fb[1] && !list_mode ? S.aov_nee : nullptr;
-        S.sh.aov_nee = fa.aov_nee;
-        S.sh.optimistic = fa.shadow_optimistic;
-
-        auto begin_timed = [&](int kind, int bounce, hipStream_t strm) {
-            if (!dev->timing) return;
-            TimedLaunch t{slot_event(S), slot_event(S), kind, bounce};
-            (void)hipEventRecord(t.a, strm);
-            S.timed.push_back(t);
-        };
-        auto end_timed = [&](hipStream_t strm) {
-            if (!dev->timing) return;
-            (void)hipEventRecord(S.timed.back().b, strm);
-        };
-
-        int chunk_pixels = (int)std::min<long long>(chunk_pixels_max, local_pixels - px0);
-        fa.chunk_pixel0 = (int)px0;
-        fa.chunk_pixels = chunk_pixels;
-        long long n = (long long)chunk_pixels * p->spi * fa.chunk_iters;
-        // tail threshold (auto): n / 64, but at most what one pass of k_finish
-        // holds (one path per resident lane): beyond that the tail kernel's
-        // lanes loop over several long paths each and it outlasts the
-        // overlapping chunk (diamond 32M-path chunks: 500K -> 196K tail paths,
-        // 204.6 -> 195.0 ms per frame, tools/sweep_frame.py)
-        // paths one pass of the tail kernel holds (lane pairs: one path per two lanes)
-        const long long fin_lanes = (long long)fin_bpc * dev->num_cus * BLOCK / (pairs ? 2 : 1);
-        const bool last_chunk = it0 + iters_per_chunk >= count && px0 + chunk_pixels_max >= local_pixels;
-        const int64_t topt = last_chunk && dev->tail_last_opt >= 0 ? dev->tail_last_opt : dev->tail_opt;
-        int tail = topt >= 0 ? (int)std::min<int64_t>(topt, 1 << 30)
-                                      : (int)std::max<long long>(32768, std::min(n / 64, fin_lanes));
-        S.tail = tail;
-        S.camera = valid_pixels_in_chunk(fa) * p->spi * fa.chunk_iters;
-        int* cnt = S.ctr; // row 2b: paths entering bounce b, row 2b+1: shadow rays of bounce b
-        auto row = [&](int r) { return cnt + (size_t)r * CROW; };
-        HIPCHK(hipMemsetAsync(S.ctr, 0, (size_t)(2 * max_bounces + 4) * CROW * sizeof(int), dev->stream));
-        if (dev->dynamic_opt)
-            HIPCHK(hipMemsetAsync(S.ctr + (size_t)WORK_ROW0 * CROW, 0, (size_t)4 * max_bounces * CROW * sizeof(int), dev->stream));
-        // camera paths: built by bounce 0 of the fused k_extend when the chunk
-        // runs through it (saves the 72 B/path round trip of k_generate)
-        const bool fuse_gen = dev->fuse_generate && !split && n > tail;
-        if (!fuse_gen) {
-            begin_timed(2, -1, dev->stream);
-            launch_generate(dev, grid_for(dev, n, 8), fa, S.pa, S.L, cnt);
-            end_timed(dev->stream);
-            HIPCHK(hipGetLastError());
-        }
-        S.n0 = n;
-        S.split = split;
-        const int fin_grid = grid_for(dev, std::min<long long>(n, tail) * (pairs ? 2 : 1), fin_bpc);
-        // Wavefront bounces on the main stream.  The host learns counts two
-        // bounces late (async copies, no per-bounce sync); the device gates
-        // k_extend off once the count is <= tail, and the host then queues
-        // k_finish for that bounce's buffer on the tail stream.
-        S.bounce_ev.clear();
-        int switch_b = -1;
-        S.launched = 0;
-        // split schedule: the shadow rays of bounce b run on the shadow stream,
-        // overlapping the trace of bounce b + 1 (independent: both come from
-        // shade(b)); shade(b + 1) waits for them, as both add to the radiance
-        // slots, so the additions keep their order and the image is unchanged
-        const bool overlap = split && dev->overlap_shadow_opt;
-        hipStream_t sh_strm = overlap ? dev->shadow_stream : dev->stream;
-        hipEvent_t sh_done = nullptr; // the last shadow launch on the shadow stream
-        if (n <= tail) switch_b = 0;
-        for (int b = 0; switch_b < 0 && b < max_bounces; ++b) {
-            long long bound = n; // paths known to remain (see the concurrent schedule)
-            if (b >= 2) {
-                HIPCHK(hipEventSynchronize(S.bounce_ev[b - 2]));
-                bound = row_total(S, 2 * (b - 1));
-                if (bound <= tail) {
-                    switch_b = b - 1;
-                    break;
+    } else {
+        // Sequential schedule: every chunk's bounces on the main stream, the
+        // slots alternating.  The host learns counts two bounces late (async
+        // copies, no per-bounce sync); the device gates k_extend off once the
+        // count is <= tail, and the host then queues k_finish for that
+        // bounce's buffer and the resolve on the tail stream and moves on.
+        const bool overlap = split && dev->overlap_shadow_opt; // shadow kernels on a stream of their own (queue_bounce)
+        const LaunchCtx ctx{dev->stream,     dev->tail_stream, overlap ? dev->shadow_stream : dev->stream,
+                            dev->spill_main, dev->spill_tail,  overlap ? dev->spill_shadow : dev->spill_main, cam};
+        for (long long k = 0, chunks = chunk_count(rp); k < chunks; ++k) {
+            const Chunk c = plan_chunk(rp, k);
+            Slot& S = dev->slots[dev->stream_slots == 1 ? 0 : dev->next_slot];
+            dev->next_slot ^= 1;
+            ChunkRun r;
+            igx_status st = begin_chunk(dev, ctx, S, plan, c, r); // waits for the chunk two chunks ago (one, with one slot)
+            if (st != IGX_OK) return st;
+            int switch_b = r.n <= r.tail ? 0 : -1;
+            for (int b = 0; switch_b < 0 && b < plan.max_bounces; ++b) {
+                long long bound = r.n; // paths known to remain
+                if (b >= 2) {
+                    HIPCHK(hipEventSynchronize(S.bounce_ev[b - 2]));
+                    bound = row_total(S, 2 * (b - 1));
+                    if (bound <= r.tail) {
+                        switch_b = b - 1;
+                        break;
+                    }
                 }
+                if (!IGX_LIVE_GRID) bound = r.n;
+                if ((st = queue_bounce(dev, ctx, S, plan, r, b, bound)) != IGX_OK) return st;
             }
-            if (!IGX_LIVE_GRID) bound = n;
-            const int ext_grid = grid_for(dev, bound, ext_bpc, dev->ext_block), tr_grid = grid_for(dev, bound, tr_bpc);
-            const int shade_grid = grid_for(dev, bound, shade_bpc), sh_grid = grid_for(dev, bound, sh_bpc);
-            PathBuf in = (b & 1) ? S.pb : S.pa, out = (b & 1) ? S.pa : S.pb;
-            KernelCounters kc{row(2 * b), row(2 * (b + 1)), row(2 * b + 1), dev->dstats, row(WORK_ROW0 + 4 * b)};
-            if (split) {
-                begin_timed(5, b, dev->stream);
-                int* const tr_work = (dev->dynamic_opt & DYN_REFILL_TRACE) ? row(WORK_ROW0 + 4 * b) : nullptr;
-                if (inst) launch_trace<true>(dev, S, tr_grid, fa, in, row(2 * b), tail, tr_work);
-                else launch_trace<false>(dev, S, tr_grid, fa, in, row(2 * b), tail, tr_work);
-                end_timed(dev->stream);
-                if (sh_done) HIPCHK(hipStreamWaitEvent(dev->stream, sh_done, 0));
-                begin_timed(0, b, dev->stream);
-                launch_shade(dev, full, shade_grid, fa, in, S.hb, out, S.sh, S.L, kc, tail);
-                end_timed(dev->stream);
-            } else {
-                begin_timed(0, b, dev->stream);
-                FrameArgs fb = fa;
-                fb.gen_n = fuse_gen && b == 0 ? (int)n : 0;
-                if (inst) launch_extend<true>(dev, S, ext_grid, fb, in, out, kc, tail);
-                else launch_extend<false>(dev, S, ext_grid, fb, in, out, kc, tail);
-                end_timed(dev->stream);
+            if (switch_b < 0) { // max_bounces launched: drain the lagged counts
+                HIPCHK(hipStreamSynchronize(ctx.main));
+                switch_b = find_switch_bounce(S, plan.max_bounces, r.tail);
             }
-            if (overlap) {
-                hipEvent_t shaded = slot_event(S);
-                HIPCHK(hipEventRecord(shaded, dev->stream));
-                HIPCHK(hipStreamWaitEvent(sh_strm, shaded, 0));
-            }
-            begin_timed(1, b, sh_strm);
-            int* const sh_work =
-                (dev->dynamic_opt & (use_refill(dev) ? DYN_REFILL_SHADOW : DYN_SHADOW)) ? row(WORK_ROW0 + 4 * b + 2) : nullptr;
-            if (inst) launch_shadow<true>(dev, S, sh_grid, row(2 * b + 1), sh_work, sh_strm);
-            else launch_shadow<false>(dev, S, sh_grid, row(2 * b + 1), sh_work, sh_strm);
-            end_timed(sh_strm);
-            if (overlap) {
-                sh_done = slot_event(S);
-                HIPCHK(hipEventRecord(sh_done, sh_strm));
-            }
-            HIPCHK(hipGetLastError());
-            // shadow counts of bounce b and path counts entering bounce b+1 (adjacent rows)
-            HIPCHK(hipMemcpyAsync(S.pinned + (size_t)(2 * b + 1) * CROW, row(2 * b + 1), 2 * CROW * sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-            hipEvent_t e = slot_event(S);
-            (void)hipEventRecord(e, dev->stream);
-            S.bounce_ev.push_back(e);
-            ++S.launched;
+            // tail + resolve on the tail stream, after the main stream (and the
+            // shadow stream's last launch) reached this point
+            if (r.sh_done) HIPCHK(hipStreamWaitEvent(ctx.main, r.sh_done, 0));
+            hipEvent_t reach = slot_event(S);
+            HIPCHK(hipEventRecord(reach, ctx.main));
+            HIPCHK(hipStreamWaitEvent(ctx.tail, reach, 0));
+            if ((st = queue_tail(dev, ctx, S, r, switch_b)) != IGX_OK || (st = queue_resolve(dev, S, r, width, ctx.tail)) != IGX_OK) return st;
         }
-        if (switch_b < 0) {
-            // max_bounces launched: drain the lagged counts and find the first bounce at/below tail
-            HIPCHK(hipStreamSynchronize(dev->stream));
-            switch_b = max_bounces;
-            for (int b = 1; b <= max_bounces; ++b)
-                if (row_total(S, 2 * b) <= tail) { switch_b = b; break; }
-        }
-        S.switch_bounce = switch_b;
-        // tail + resolve on the tail stream, after the main stream (and the
-        // shadow stream's last launch) reached this point
-        if (sh_done) HIPCHK(hipStreamWaitEvent(dev->stream, sh_done, 0));
-        hipEvent_t reach = slot_event(S);
-        HIPCHK(hipEventRecord(reach, dev->stream));
-        HIPCHK(hipStreamWaitEvent(dev->tail_stream, reach, 0));
-        if (switch_b < MAX_BOUNCES) {
-            PathBuf in = (switch_b & 1) ? S.pb : S.pa;
-            begin_timed(4, switch_b, dev->tail_stream);
-            if (inst) launch_finish<true>(dev, S, fin_grid, fa, in, row(2 * switch_b), tail);
-            else launch_finish<false>(dev, S, fin_grid, fa, in, row(2 * switch_b), tail);
-            end_timed(dev->tail_stream);
-        }
-        begin_timed(3, -1, dev->tail_stream);
-        hipLaunchKernelGGL(k_resolve, dim3((chunk_pixels + 63) / 64), dim3(64 * RES_G), 0, dev->tail_stream, fa, S.L, dev->fb, width);
-        if (fa.aov_di)
-            for (int k = 0; k < 2; ++k)
-                hipLaunchKernelGGL(k_resolve, dim3((chunk_pixels + 63) / 64), dim3(64 * RES_G), 0, dev->tail_stream, fa,
-                                   k ? S.aov_nee : S.aov_di, dev->aov_fb[k], width);
-        end_timed(dev->tail_stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(S.done, dev->tail_stream));
-        S.pending = true;
+        dev->iteration_count += count;
+        dev->stats.iterations += count;
     }
-    dev->iteration_count += count;
-    dev->stats.iterations += count;
     dev->stats.ms_render += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     return IGX_OK;
 }

@@ -840,6 +840,40 @@ def test_async_render_queue_matches_synchronous(diamond_path):
     assert rays[0] == rays[1]
 
 
+@pytest.mark.parametrize("tail", [0, 1 << 30])
+def test_schedules_share_chunk_steps(diamond_path, tail):
+    """The sequential schedule, the concurrent one and the concurrent one on
+    the async worker run the same chunk steps: three iterations in one call,
+    cut into chunks of one iteration's paths, with every path in the wavefront
+    bounces (tail_threshold 0) or every chunk one tail pass (1 << 30), leave
+    bit-identical films and equal ray, iteration and tail-launch counts."""
+    sc = ignis_amd.Scene.from_file(diamond_path)
+    w, h, spi, iters = 100, 100, 2, 3
+    films, counts = [], []
+    for conc, asy in ((0, 0), (1, 0), (1, 1)):
+        d = ignis_amd.Device(0)
+        d.upload(sc)
+        d.set_option("concurrent_chunks", conc)
+        d.set_option("async_render", asy)
+        d.set_option("capacity", 20000)
+        d.set_option("tail_threshold", tail)
+        p = ignis_amd.RenderParams()
+        p.width, p.height, p.spi = w, h, spi
+        d.render_iterations(p, iters)
+        fb, n = d.framebuffer(w * h * 3)
+        st = d.stats()
+        assert n == iters
+        films.append(fb)
+        counts.append((st["camera_rays"], st["bounce_rays"] + st["tail_bounce_rays"], st["shadow_rays"] + st["tail_shadow_rays"],
+                       st["iterations"], st["launches_finish"]))
+        d.close()
+    np.testing.assert_array_equal(films[0], films[1])
+    np.testing.assert_array_equal(films[0], films[2])
+    assert films[0].sum() > 0
+    assert counts[0] == counts[1] == counts[2]
+    assert counts[0][0] == w * h * spi * iters and counts[0][3] == iters
+
+
 def test_async_worker_failure_is_sticky_until_clear(diamond_path):
     """A chunk that fails on the async worker (test hook "fail_chunk") drops the
     queue, so film and iteration count no longer agree: every later call that
