@@ -104,12 +104,15 @@ struct DevMaterial {   // 128 B
     float kappa[4];     // conductor k; w = alpha_v
     float pad[8];       // textured diffuse (igx_material::texture): pad[0] = texture (int bits),
                         // pad[1] = scale, pad[2..4] = the colour where the checker is 1 (kd elsewhere)
+                        // image texture (IGX_TEXTURE_IMAGE, also on a principled base_color): pad[1..6] =
+                        // the 2x3 uv transform, pad[7] = its TexRecord's place in the uv table (uint bits)
 };
 
 enum : int32_t { LIGHT_PLANE = 1, LIGHT_ENV = 2, LIGHT_POINT = 3, LIGHT_SPOT = 4, LIGHT_DIRECTIONAL = 5, LIGHT_SUN = 6,
-                   LIGHT_SPHERE = 7, LIGHT_MESH = 8, LIGHT_CIE = 9 };
+                   LIGHT_SPHERE = 7, LIGHT_MESH = 8, LIGHT_CIE = 9, LIGHT_ENVMAP = 10 };
 // A CIE sky (LIGHT_CIE, host/cie_sky.h) keeps its CieSky record in the 28
-// floats from `radiance` on (cie_sky_of); `entity` is unused.
+// floats from `radiance` on (cie_sky_of); `entity` is unused.  An image
+// environment map (LIGHT_ENVMAP, host/image_texture.h) keeps its EnvMap there.
 struct DevLight {      // 128 B
     int32_t type, infinite, delta, entity; // entity: emitting entity of sphere / mesh area lights
     float radiance[4];

@@ -608,18 +608,36 @@ __device__ __forceinline__ void ray_extent(const FrameArgs& fa, const SceneView&
 // select(checkerboard(uvw * scale) == 1, kd1, kd) of texture/checkerboard.art:2
 // on the texture coordinates (u, v, 0), interpolated with the hit's
 // barycentrics (vec2_lerp2, shapes/trimesh.art:25; core/vector.art:150-153);
-// math::wrap(x, 0, 2) as i32 % 2 per axis (core/math.art:88-91)
+// math::wrap(x, 0, 2) as i32 % 2 per axis (core/math.art:88-91); or an image
+// texture (texture/image.art)
 __device__ __forceinline__ int checker_bit(float x) {
     const float w = x - 2.0f * floorf(x / 2.0f);
     return ((int)w) % 2;
 }
 __device__ __forceinline__ void apply_texture(const SceneView& sv, DevMaterial& m, int ent_id, int prim, float hu, float hv) {
-    if (__float_as_int(m.pad[0]) != 1) return;
+    const int kind = __float_as_int(m.pad[0]);
+    if (kind != 1 && kind != 2) return;
     const int4 info = *reinterpret_cast<const int4*>(sv.ent + ENT_STRIDE * ent_id + 6); // shape type, material, vtx_off, idx_off
     if (info.x == 1) return; // analytic sphere: refused at upload
     const int4 f = sv.idx[info.w + prim];
     const float2 t0 = sv.uv[info.z + f.x], t1 = sv.uv[info.z + f.y], t2 = sv.uv[info.z + f.z];
     const float u = lerp2(t0.x, t1.x, t2.x, hu, hv), v = lerp2(t0.y, t1.y, t2.y, hu, hv);
+    if (kind == 2) {
+        // An image texture (host/image_texture.h): pad[1..6] its 2x3 uv transform,
+        // pad[7] the place of its TexRecord in the uv table, which names filter,
+        // wrap, size and texels.  The colour replaces kd (diffuse reflectance,
+        // principled base_color); alpha is not used.
+        const TexRecord rec = *reinterpret_cast<const TexRecord*>(sv.uv + __float_as_uint(m.pad[7]));
+        const void* const texels = sv.uv + rec.texels;
+        float tu, tv;
+        tex_transform(&m.pad[1], u, v, tu, tv);
+        const Texel c = tex_filter(rec.filter, rec.wrap_u, rec.wrap_v, rec.width, rec.height, tu, tv,
+                                   [&](int x, int y) { return tex_fetch(rec.format, texels, rec.width, x, y); });
+        m.kd[0] = c.r;
+        m.kd[1] = c.g;
+        m.kd[2] = c.b;
+        return;
+    }
     const float sc = m.pad[1];
     // node_checkerboard3(uvw * sc): ((a == b) == (c == 1)) with c of the zero w
     const int a = checker_bit(u * sc), b = checker_bit(v * sc), c = checker_bit(0.0f * sc);
@@ -661,10 +679,19 @@ __device__ __forceinline__ bool shade_step(const FrameArgs& fa, const SceneView&
             if (Lt.delta) continue;
             f3 emit = mk(Lt.radiance[0], Lt.radiance[1], Lt.radiance[2]);
             float pdf_s = 1 / (4 * PI_);
-            if constexpr (FULL)
+            // a direction NEE never takes (below a hemispherical sky, darker than a compensated
+            // map's mean) belongs to BSDF sampling alone; without this a grazing bounce, whose own
+            // pdf is 0 and inv_pdf infinite, would weigh it by 1 / (1 + inf * 0)
+            bool nee_blind = false;
+            if constexpr (FULL) {
                 if (Lt.type == LIGHT_CIE) cie_emission(Lt, rd, emit, pdf_s);
+                else if (Lt.type == LIGHT_ENVMAP) env_map_emission(sv, Lt, rd, emit, pdf_s);
+                nee_blind = !(pdf_s > 0);
+            }
             const float sel = sv.selector == SEL_UNIFORM ? 1.0f / (float)sv.num_lights : select_pdf(sv, li, ps.o);
             float mis = sv.nee ? 1 / (1 + ps.inv_pdf * sel * pdf_s) : 1.0f;
+            if constexpr (FULL)
+                if (nee_blind) mis = 1.0f;
             Lacc = add(Lacc, handle_color(sv, mulf(mul(ps.contrib, emit), mis)));
             has_l = true;
         }
@@ -2110,6 +2137,7 @@ struct igx_device {
     size_t lds_per_block = 64 * 1024;  // device attribute: LDS one workgroup may take
     size_t table_bytes = 0;            // traversal tables (nodes, instances, triangles) of the current scene
     size_t shading_bytes = 0;          // shading tables (entities, vertices, normals, faces, materials, lights)
+    size_t image_bytes = 0, cdf_bytes = 0; // image textures' texels and environment maps' sampling tables (in the uv table)
     int leaf_size = 4;
     // stream class of surviving paths (FrameArgs::classify; option "path_classes"):
     // paths inside a dielectric go to the back of their shard, so the next
@@ -3374,6 +3402,8 @@ extern "C" igx_status igx_upload_scene(igx_device* dev, const igx_scene_desc* de
                          t.idx.size() * sizeof(t.idx[0]) + t.mats.size() * sizeof(DevMaterial) +
                          t.lights.size() * sizeof(t.lights[0]) + t.fn_tab.size() * sizeof(t.fn_tab[0]) +
                          t.fsh.size() * sizeof(t.fsh[0]);
+    dev->image_bytes = t.image_bytes;
+    dev->cdf_bytes = t.cdf_bytes;
     dev->cam_desc = desc->camera;
     dev->rays_w = desc->film_width;
     dev->rays_h = desc->film_height;
@@ -4584,6 +4614,8 @@ extern "C" igx_status igx_get_stats(igx_device* dev, igx_stats* out) {
     out->treelet_nodes[3] = 0; // tail kernels: no treelet
     out->table_bytes = dev->table_bytes;
     out->shading_bytes = dev->shading_bytes;
+    out->image_bytes = dev->image_bytes;
+    out->cdf_bytes = dev->cdf_bytes;
     out->slot_bytes = 0;
     for (const Slot& s : dev->slots)
         out->slot_bytes += (uint64_t)s.shard_cap * NSH * (2 * 56 * (s.pa.c_base ? 2 : 1) + 48 + (s.hb.h ? 20 : 0)) +

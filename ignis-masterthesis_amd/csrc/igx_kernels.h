@@ -9,6 +9,7 @@
 #include "device_math.h"
 #include "device_scene.h"
 #include "../host/cie_sky.h"
+#include "../host/image_texture.h"
 
 #include <cstddef>
 
@@ -1164,6 +1165,37 @@ __device__ __forceinline__ void cie_emission(const DevLight& L, f3 rd, f3& emit,
     }
 }
 
+// ---- image environment maps (LIGHT_ENVMAP, host/image_texture.h; full shading variant only) ----
+// make_environment_light_textured, or make_environment_light where the map has
+// no CDF (light/env.art:112-164).  The record, the texture's TexRecord, its
+// texels and the CDF all live in the uv table (SceneView::uv).
+__device__ __forceinline__ const EnvMap& env_map_of(const DevLight& L) { return *reinterpret_cast<const EnvMap*>(L.radiance); }
+// scale * tex(uv) at the map coordinates uv
+__device__ __forceinline__ f3 env_map_radiance(const SceneView& sv, const EnvMap& e, float u, float v) {
+    const TexRecord rec = *reinterpret_cast<const TexRecord*>(sv.uv + e.texture);
+    const void* const texels = sv.uv + rec.texels;
+    float tu, tv;
+    tex_transform(e.uv_transform, u, v, tu, tv);
+    const Texel c = tex_filter(rec.filter, rec.wrap_u, rec.wrap_v, rec.width, rec.height, tu, tv,
+                               [&](int x, int y) { return tex_fetch(rec.format, texels, rec.width, x, y); });
+    return mk(e.scale[0] * c.r, e.scale[1] * c.g, e.scale[2] * c.b);
+}
+// Light::emission and pdf_direct (solid angle) for the ray direction `rd`
+// leaving the scene (env.art:127-133, 146-152)
+__device__ __forceinline__ void env_map_emission(const SceneView& sv, const DevLight& L, f3 rd, f3& emit, float& pdf_s) {
+    const EnvMap& e = env_map_of(L);
+    const EnvVec local = env_to_local(e, EnvVec{rd.x, rd.y, rd.z});
+    float u, v;
+    map_env_uv(local, u, v);
+    emit = env_map_radiance(sv, e, u, v);
+    if (e.cdf_w > 0) {
+        const float* const cdf = reinterpret_cast<const float*>(sv.uv + e.cdf);
+        pdf_s = env_pdf_solid(cdf2d_pdf_continuous(cdf, e.cdf_w, e.cdf_h, u, v), env_sin_theta(local));
+    } else {
+        pdf_s = 1 / (4 * PI_);
+    }
+}
+
 // Light::sample_direct for the light types on the hot path
 template <bool FULL>
 __device__ __forceinline__ DirectSample light_sample_direct(const SceneView& sv, const DevLight& L, Rng& rnd,
@@ -1238,6 +1270,40 @@ __device__ __forceinline__ DirectSample light_sample_direct(const SceneView& sv,
         ds.pos = add(from.point, mulf(dir, sv.scene_radius));
         ds.dir = dir;
         ds.pdf_value = pdf;
+        ds.pdf_solid = true;
+        ds.cos = 1.0f;
+        ds.dist = sv.scene_radius;
+    } else if (FULL && L.type == LIGHT_ENVMAP) {
+        const EnvMap& e = env_map_of(L);
+        float ux = rnd.next_f32();
+        float uy = rnd.next_f32();
+        f3 dir, rad_e;
+        float pdf;
+        if (e.cdf_w > 0) {
+            // make_environment_light_textured.sample_direct (env.art:115-125, 137-140) with
+            // cdf::sample_continuous; here the sampled radiance carries `scale` as the seen one does
+            const float* const cdf = reinterpret_cast<const float*>(sv.uv + e.cdf);
+            float px, py, pdf_uv;
+            cdf2d_sample_continuous(cdf, e.cdf_w, e.cdf_h, ux, uy, px, py, pdf_uv);
+            rad_e = env_map_radiance(sv, e, px, py);
+            const EnvVec local = env_dir_from_uv(px, py);
+            pdf = env_pdf_solid(pdf_uv, env_sin_theta(local));
+            const EnvVec g = env_to_world(e, local);
+            dir = mk(g.x, g.y, g.z);
+        } else {
+            // make_environment_light (env.art:161-164): uniform over the sphere
+            dir = equal_area_square_to_sphere(ux, uy);
+            pdf = 1 / (4 * PI_);
+            const EnvVec local = env_to_local(e, EnvVec{dir.x, dir.y, dir.z});
+            float u, v;
+            map_env_uv(local, u, v);
+            rad_e = env_map_radiance(sv, e, u, v);
+        }
+        // a direction of zero density (a pole of the map) carries nothing
+        ds.intensity = pdf > 0 ? mulf(rad_e, 1 / pdf) : mk(0, 0, 0);
+        ds.pos = add(from.point, mulf(dir, sv.scene_radius));
+        ds.dir = dir;
+        ds.pdf_value = pdf > 0 ? pdf : 1.0f;
         ds.pdf_solid = true;
         ds.cos = 1.0f;
         ds.dist = sv.scene_radius;

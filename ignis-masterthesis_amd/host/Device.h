@@ -204,6 +204,12 @@ public:
         qty("BounceRays", mStats.bounce_rays);
         qty("PrimaryRays", mStats.camera_rays + mStats.bounce_rays);
         qty("TotalRays", mStats.camera_rays + mStats.bounce_rays + mStats.shadow_rays);
+        if (mStats.image_bytes || mStats.cdf_bytes) {
+            char b[160];
+            std::snprintf(b, sizeof(b), "  Image textures:\n  |-%-12s %llu bytes\n  |-%-12s %llu bytes\n", "Texels",
+                          (unsigned long long)mStats.image_bytes, "EnvCDF", (unsigned long long)mStats.cdf_bytes);
+            out += b;
+        }
         return out;
     }
     igx_stats mStats{};
@@ -447,6 +453,9 @@ private:
         igx_technique technique{};
         std::vector<igx_material> materials;
         std::vector<igx_light> lights;
+        std::vector<igx_image> images; // headers and texel addresses: texels behind an unchanged address count as
+                                       // unchanged (igx_shading_view in igx_scene.h states the rule)
+        std::vector<igx_texture> textures;
         void take(const igx_shading_view& v) {
             valid = true;
             film_width = v.film_width;
@@ -454,11 +463,23 @@ private:
             technique = v.technique;
             materials.assign(v.materials, v.materials + v.num_materials);
             lights.assign(v.lights, v.lights + v.num_lights);
+            images.assign(v.images, v.images + v.num_images);
+            textures.assign(v.textures, v.textures + v.num_textures);
+        }
+        // field by field: igx_image has padding bytes, whose content says nothing
+        bool same_images(const igx_shading_view& v) const {
+            for (size_t i = 0; i < images.size(); ++i) {
+                const igx_image &a = images[i], &b = v.images[i];
+                if (a.width != b.width || a.height != b.height || a.format != b.format || a.pixels != b.pixels) return false;
+            }
+            return true;
         }
         bool same(const igx_shading_view& v) const {
             return valid && film_width == v.film_width && film_height == v.film_height &&
                    std::memcmp(&technique, &v.technique, sizeof(technique)) == 0 && materials.size() == v.num_materials &&
-                   lights.size() == v.num_lights &&
+                   lights.size() == v.num_lights && images.size() == v.num_images && textures.size() == v.num_textures &&
+                   same_images(v) &&
+                   (textures.empty() || std::memcmp(textures.data(), v.textures, textures.size() * sizeof(igx_texture)) == 0) &&
                    (materials.empty() || std::memcmp(materials.data(), v.materials, materials.size() * sizeof(igx_material)) == 0) &&
                    (lights.empty() || std::memcmp(lights.data(), v.lights, lights.size() * sizeof(igx_light)) == 0);
         }

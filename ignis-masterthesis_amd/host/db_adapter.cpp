@@ -241,6 +241,24 @@ static void build_from_tables(SceneStore& S, const igx_database_view& db, const 
         if (L.entity >= 0 && (uint64_t)L.entity >= ne) fail("lights: area light entity beyond the entity table");
     for (const igx_material& m : S.materials)
         if (m.light >= (int32_t)S.lights.size()) fail("materials: light index beyond the light table");
+    // image textures: the texels are copied, the indices checked
+    if ((sh.num_images && !sh.images) || (sh.num_textures && !sh.textures)) fail("textures: null image or texture table");
+    for (uint32_t i = 0; i < sh.num_images; ++i) {
+        const igx_image& im = sh.images[i];
+        if (im.width < 1 || im.height < 1 || im.width > 16384 || im.height > 16384 || !im.pixels || im.format < IGX_IMAGE_RGBA8 ||
+            im.format > IGX_IMAGE_FLOAT4)
+            fail("textures: invalid image " + std::to_string(i));
+        const size_t bytes = (size_t)im.width * im.height * (im.format == IGX_IMAGE_FLOAT4 ? 16 : im.format == IGX_IMAGE_MONO8 ? 1 : 4);
+        const uint8_t* p = static_cast<const uint8_t*>(im.pixels);
+        S.image_pixels.emplace_back(p, p + bytes);
+        S.images.push_back(im);
+    }
+    S.textures.assign(sh.textures, sh.textures + sh.num_textures);
+    for (const igx_texture& t : S.textures)
+        if (t.image < 0 || (uint32_t)t.image >= sh.num_images) fail("textures: image index beyond the image table");
+    for (const igx_material& m : S.materials)
+        if (m.texture == IGX_TEXTURE_IMAGE && (m.tex_index < 0 || (uint32_t)m.tex_index >= sh.num_textures))
+            fail("materials: texture index beyond the texture table");
     S.desc.film_width = sh.film_width;
     S.desc.film_height = sh.film_height;
     S.desc.camera = sh.camera;

@@ -201,6 +201,10 @@ void serialize_scene(const igx_scene_desc& desc, SceneDatabase& db, igx_shading_
     shading.materials = desc.materials;
     shading.num_lights = desc.num_lights;
     shading.lights = desc.lights;
+    shading.num_images = desc.num_images;
+    shading.images = desc.images;
+    shading.num_textures = desc.num_textures;
+    shading.textures = desc.textures;
 }
 
 } // namespace IG

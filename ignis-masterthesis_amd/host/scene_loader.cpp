@@ -13,6 +13,7 @@
 #include "mesh.h"
 #include "scene_store.h"
 #include "cie_sky.h"
+#include "image_io.h"
 #include "sun_position.h"
 
 #include <cctype>
@@ -585,6 +586,75 @@ static void build_scene(SceneStore& S, const Value& doc, const std::string& base
     }
     S.desc.technique = tech;
 
+    // ---- textures (ImagePattern::serialize, pattern/ImagePattern.cpp:19-52) ----
+    // Image textures only, and only where a colour property names one: its file
+    // is read then, once per (file, linear).  Every other texture type stays
+    // unknown to the colour properties, which refuse its name as before.
+    std::unordered_map<std::string, const Value*> image_textures;
+    if (const Value* arr = array_of(doc, "textures"))
+        for (auto& t : arr->arr) {
+            Props tp{&t};
+            if (tp.string("type") == "image") image_textures[tp.string("name")] = &t;
+        }
+    std::unordered_map<std::string, int32_t> texture_ids, image_ids;
+    // index of the image texture `expr` names in S.textures, -1 if it names none
+    auto image_texture_named = [&](const std::string& expr) -> int32_t {
+        auto decl = image_textures.find(expr);
+        if (decl == image_textures.end()) return -1;
+        auto known = texture_ids.find(expr);
+        if (known != texture_ids.end()) return known->second;
+        Props tp{decl->second};
+        const std::string tname = "texture '" + expr + "': ";
+        if (!tp.has("filename")) fail(tname + "no filename");
+        const Value* obj_dir = decl->second->find("__base_dir");
+        const std::string file = join_path(obj_dir && obj_dir->is_string() ? obj_dir->str : base_dir, tp.string("filename"));
+        const bool linear = tp.boolean("linear", false);
+        if (tp.boolean("force_unpacked", false)) fail(tname + "force_unpacked is not supported");
+        igx_texture t{};
+        const std::string image_key = file + (linear ? "|linear" : "|srgb");
+        auto img = image_ids.find(image_key);
+        if (img == image_ids.end()) {
+            igx::LoadedImage li = igx::load_image_file(file, linear);
+            igx_image im{};
+            im.width = li.width;
+            im.height = li.height;
+            im.format = li.format;
+            S.images.push_back(im);
+            S.image_pixels.push_back(std::move(li.pixels));
+            img = image_ids.emplace(image_key, (int32_t)S.images.size() - 1).first;
+        }
+        t.image = img->second;
+        const std::string filter = tp.string("filter_type", "bicubic");
+        t.filter = filter == "bilinear" ? IGX_FILTER_BILINEAR : filter == "nearest" ? IGX_FILTER_NEAREST : IGX_FILTER_BICUBIC;
+        auto wrap_of = [](const std::string& s) { return s == "mirror" ? IGX_WRAP_MIRROR : s == "clamp" ? IGX_WRAP_CLAMP : IGX_WRAP_REPEAT; };
+        if (tp.has("wrap_mode_u")) {
+            t.wrap_u = wrap_of(tp.string("wrap_mode_u", "repeat"));
+            t.wrap_v = wrap_of(tp.string("wrap_mode_v", "repeat"));
+        } else {
+            t.wrap_u = t.wrap_v = wrap_of(tp.string("wrap_mode", "repeat"));
+        }
+        // LoaderUtils::inlineTransformAs2d: the upper-left 2x2 block and the x, y translation
+        const M4 m = get_transform(tp);
+        const float m23[6] = {m.at(0, 0), m.at(0, 1), m.at(0, 3), m.at(1, 0), m.at(1, 1), m.at(1, 3)};
+        std::memcpy(t.transform, m23, sizeof(m23));
+        S.textures.push_back(t);
+        return texture_ids[expr] = (int32_t)S.textures.size() - 1;
+    };
+    // a colour property that may name an image texture (the form the Blender
+    // exporter writes): the material then takes its colour from the texture
+    auto textured_color = [&](const Props& bp, const char* key, V3 def, igx_material& m) -> V3 {
+        const Value* p = bp.get(key);
+        if (p && p->is_string()) {
+            const int32_t t = image_texture_named(p->str);
+            if (t >= 0) {
+                m.texture = IGX_TEXTURE_IMAGE;
+                m.tex_index = t;
+                return def;
+            }
+        }
+        return bp.color(key, def);
+    };
+
     // ---- bsdfs ----
     std::unordered_map<std::string, igx_material> bsdfs;
     if (const Value* arr = array_of(doc, "bsdfs")) {
@@ -594,6 +664,7 @@ static void build_scene(SceneStore& S, const Value& doc, const std::string& base
             std::string type = bp.string("type");
             igx_material m{};
             m.light = -1;
+            m.tex_index = -1;
             m.ext_ior = 1.0f;
             m.int_ior = 1.5046f;
             m.kd[0] = m.kd[1] = m.kd[2] = 0.8f;
@@ -609,7 +680,7 @@ static void build_scene(SceneStore& S, const Value& doc, const std::string& base
                     m.tex_scale = scale;
                     m.tex_kd1[0] = kd1.x; m.tex_kd1[1] = kd1.y; m.tex_kd1[2] = kd1.z;
                 } else {
-                    kd = bp.color("reflectance", V3(0.8f, 0.8f, 0.8f)); // DiffuseBSDF.cpp:17
+                    kd = textured_color(bp, "reflectance", V3(0.8f, 0.8f, 0.8f), m); // DiffuseBSDF.cpp:17
                 }
                 m.kd[0] = kd.x; m.kd[1] = kd.y; m.kd[2] = kd.z;
                 m.diffuse_alpha = bp.number(bp.has("alpha") ? "alpha" : "roughness", 0.0f); // Oren-Nayar above flt_eps
@@ -649,7 +720,7 @@ static void build_scene(SceneStore& S, const Value& doc, const std::string& base
             } else if (type == "principled") {
                 // PrincipledBSDF::serialize (PrincipledBSDF.cpp:11-60)
                 m.bsdf_type = IGX_BSDF_PRINCIPLED;
-                V3 base = bp.color("base_color", V3(0.8f, 0.8f, 0.8f));
+                V3 base = textured_color(bp, "base_color", V3(0.8f, 0.8f, 0.8f), m);
                 m.kd[0] = base.x; m.kd[1] = base.y; m.kd[2] = base.z;
                 const std::string ior_mat = bp.string("ior_material", "");
                 m.ior = bp.number("ior", dielectric_ior(ior_mat.empty() ? "bk7" : ior_mat, name));
@@ -896,14 +967,41 @@ static void build_scene(SceneStore& S, const Value& doc, const std::string& base
                 S.materials[ent.material].light = (int)S.lights.size();
             } else if (type == "env" || type == "constant" || type == "uniform") {
                 // EnvironmentLight.cpp:28-78: constant radiance bakes to a 1x1 texture -> make_environment_light
-                // a constant colour expression is accepted (Props::color); an image or
-                // a varying expression is a textured environment (not supported).
+                // a constant colour expression is accepted (Props::color); the name of an
+                // image texture makes an image environment map; any other varying
+                // expression is not supported.
                 // The light's transform only rotates the texture lookup: without
                 // effect on a constant environment
-                V3 rad = lp.color("radiance", V3(1, 1, 1));
                 V3 scale = lp.color("scale", V3(1, 1, 1));
-                L.type = IGX_LIGHT_ENV;
-                for (int i = 0; i < 3; ++i) L.radiance[i] = rad[i] * scale[i];
+                const Value* radiance = lp.get("radiance");
+                const int32_t env_tex = radiance && radiance->is_string() ? image_texture_named(radiance->str) : -1;
+                if (env_tex >= 0) {
+                    // an image environment map (EnvironmentLight.cpp:10-74)
+                    std::string method = lp.string("cdf_method", "");
+                    for (auto& c : method) c = (char)std::tolower(c);
+                    if (method == "sat") fail("light '" + name + "': cdf_method 'sat' is not supported (the conditional CDF is)");
+                    L.type = IGX_LIGHT_ENVMAP;
+                    L.env_texture = env_tex;
+                    L.env_cdf = lp.boolean("cdf", true) ? 1 : 0;
+                    L.env_compensate = lp.boolean("compensate", true) ? 1 : 0;
+                    for (int i = 0; i < 3; ++i) {
+                        L.env_scale[i] = scale[i];
+                        L.radiance[i] = 1.0f;
+                    }
+                    // transform.linear().transpose().inverse() through inlineMatrix, as for a CIE sky
+                    const igx::M3 tm = igx::inverse3(igx::transpose3(igx::linear_of(get_transform(lp))));
+                    bool identity = true;
+                    for (int i = 0; i < 9; ++i) identity = identity && std::abs(tm.m[i] - (i % 4 == 0 ? 1.0f : 0.0f)) <= 1e-5f;
+                    for (int i = 0; i < 9; ++i) L.sky_transform[i] = identity ? (i % 4 == 0 ? 1.0f : 0.0f) : igxd::cie_printed(tm.m[i]);
+                    // EnvironmentLight::computeFlux (EnvironmentLight.cpp:19-25): a texture counts as radiance 1
+                    const V3 diam = scene_bbox.empty() ? V3() : scene_bbox.diameter();
+                    const float radius = igx::norm(diam) / 2;
+                    L.select_flux = (scale.x + scale.y + scale.z) / 3 * kPi * radius * radius;
+                } else {
+                    V3 rad = lp.color("radiance", V3(1, 1, 1));
+                    L.type = IGX_LIGHT_ENV;
+                    for (int i = 0; i < 3; ++i) L.radiance[i] = rad[i] * scale[i];
+                }
             } else if (type == "point") {
                 V3 pos = lp.vec3("position", V3());
                 // PointLight.cpp:16-30, 61-69: with `power` the intensity is power / (4 pi)

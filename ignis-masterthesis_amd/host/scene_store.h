@@ -21,6 +21,10 @@ struct SceneStore {
     std::vector<igx_entity> entities;
     std::vector<igx_material> materials;
     std::vector<igx_light> lights;
+    // image textures: the texels of images[i] are image_pixels[i]
+    std::vector<std::vector<uint8_t>> image_pixels;
+    std::vector<igx_image> images;
+    std::vector<igx_texture> textures;
     // names (JSON loader only): entity names, and per material id its BSDF
     // name and emissive entity (LoaderContext::Material, LoaderContext.h:19-27)
     std::vector<std::string> entity_names;
@@ -38,6 +42,11 @@ struct SceneStore {
         desc.materials = materials.data();
         desc.num_lights = (uint32_t)lights.size();
         desc.lights = lights.data();
+        for (size_t i = 0; i < images.size(); ++i) images[i].pixels = image_pixels[i].data();
+        desc.num_images = (uint32_t)images.size();
+        desc.images = images.data();
+        desc.num_textures = (uint32_t)textures.size();
+        desc.textures = textures.data();
     }
 };
 

@@ -1,6 +1,8 @@
 // build_scene_tables: an igx_scene_desc as the device's flat tables (scene_tables.h).
 #include "scene_tables.h"
 
+#include "env_cdf.h"
+
 #include "cie_sky.h"
 
 #include <algorithm>
@@ -490,12 +492,13 @@ igx_status build_scene_tables(const igx_scene_desc& desc, const SceneBuildOption
 
     // ---- materials and lights (infinite lights first) --------------------
     std::vector<int> light_remap(desc.num_lights, -1);
+    bool env_mapped = false; // an image environment map: the texture table is needed without a textured material, too
     auto& lights = out.lights;
     for (int pass = 0; pass < 2; ++pass)
         for (uint32_t l = 0; l < desc.num_lights; ++l) {
             const igx_light& L = desc.lights[l];
             bool infinite = L.type == IGX_LIGHT_ENV || L.type == IGX_LIGHT_DIRECTIONAL || L.type == IGX_LIGHT_SUN ||
-                            L.type == IGX_LIGHT_CIE; // a sky is infinite and not delta
+                            L.type == IGX_LIGHT_CIE || L.type == IGX_LIGHT_ENVMAP; // a sky is infinite and not delta
             if ((pass == 0) != infinite) continue;
             DevLight d{};
             d.type = L.type;
@@ -559,6 +562,11 @@ igx_status build_scene_tables(const igx_scene_desc& desc, const SceneBuildOption
                 static_assert(offsetof(DevLight, radiance) == 16 && sizeof(DevLight) == 16 + sizeof(CieSky), "CieSky lives behind the DevLight header");
                 const CieSky sky = make_cie_sky(L);
                 std::memcpy(d.radiance, &sky, sizeof(sky));
+            } else if (L.type == IGX_LIGHT_ENVMAP) {
+                // its EnvMap record follows once the texture table stands (below)
+                if (L.env_texture < 0 || (uint32_t)L.env_texture >= desc.num_textures)
+                    return fail(IGX_ERR_INVALID_ARGUMENT, "environment map: texture index beyond the texture table");
+                env_mapped = true;
             } else if (L.type != IGX_LIGHT_ENV) {
                 return fail(IGX_ERR_UNSUPPORTED, "unsupported light type");
             }
@@ -573,6 +581,76 @@ igx_status build_scene_tables(const igx_scene_desc& desc, const SceneBuildOption
         if (light_remap[l] >= num_infinite) finite_lights.push_back(desc.lights[l]);
     // (pass 1 above numbers the finite lights in desc order, so this is device order)
     out.lsel = build_light_select(desc.technique.light_selector, (int)lights.size(), finite_lights);
+    // Image textures: behind the texture coordinates, the uv table carries one
+    // TexRecord per texture (32-B aligned) and then the texels of every image
+    // (16-B aligned), so a lookup needs no further table pointer: the material
+    // names its record, the record its texels, both as offsets into the table.
+    std::vector<uint32_t> tex_record_at(desc.num_textures, 0); // in Float2 units
+    if ((textured || env_mapped) && desc.num_textures) {
+        if (!desc.textures || !desc.images) return fail(IGX_ERR_INVALID_ARGUMENT, "null texture or image table");
+        auto pad_to = [&](size_t unit) { uvs.resize((uvs.size() + unit - 1) / unit * unit, Float2{0, 0}); };
+        std::vector<uint32_t> image_at(desc.num_images, 0);
+        size_t total = (uvs.size() + 3) / 4 * 4 + 4 * (size_t)desc.num_textures;
+        for (uint32_t i = 0; i < desc.num_images; ++i) {
+            const igx_image& im = desc.images[i];
+            if (im.width < 1 || im.height < 1 || im.width > 16384 || im.height > 16384 || !im.pixels || im.format < IGX_IMAGE_RGBA8 ||
+                im.format > IGX_IMAGE_FLOAT4)
+                return fail(IGX_ERR_INVALID_ARGUMENT, "invalid image " + std::to_string(i));
+            const size_t bytes = (size_t)im.width * im.height * (im.format == IGX_IMAGE_FLOAT4 ? 16 : im.format == IGX_IMAGE_MONO8 ? 1 : 4);
+            total = (total + 1) / 2 * 2 + (bytes + 7) / 8;
+        }
+        if (total > 0x7fffffffu) return fail(IGX_ERR_UNSUPPORTED, "texture coordinates and images exceed 16 GB");
+        pad_to(4);
+        const size_t records = uvs.size();
+        uvs.resize(records + 4 * (size_t)desc.num_textures, Float2{0, 0});
+        for (uint32_t i = 0; i < desc.num_images; ++i) {
+            const igx_image& im = desc.images[i];
+            const size_t bytes = (size_t)im.width * im.height * (im.format == IGX_IMAGE_FLOAT4 ? 16 : im.format == IGX_IMAGE_MONO8 ? 1 : 4);
+            pad_to(2);
+            image_at[i] = (uint32_t)uvs.size();
+            uvs.resize(uvs.size() + (bytes + 7) / 8, Float2{0, 0});
+            std::memcpy(reinterpret_cast<uint8_t*>(uvs.data() + image_at[i]), im.pixels, bytes);
+            out.image_bytes += bytes;
+        }
+        for (uint32_t t = 0; t < desc.num_textures; ++t) {
+            const igx_texture& tx = desc.textures[t];
+            if (tx.image < 0 || (uint32_t)tx.image >= desc.num_images || tx.filter < IGX_FILTER_NEAREST || tx.filter > IGX_FILTER_BICUBIC ||
+                tx.wrap_u < IGX_WRAP_REPEAT || tx.wrap_u > IGX_WRAP_MIRROR || tx.wrap_v < IGX_WRAP_REPEAT || tx.wrap_v > IGX_WRAP_MIRROR)
+                return fail(IGX_ERR_INVALID_ARGUMENT, "invalid texture " + std::to_string(t));
+            const igx_image& im = desc.images[tx.image];
+            const TexRecord r{im.width, im.height, im.format, tx.filter, tx.wrap_u, tx.wrap_v, image_at[tx.image], 0};
+            tex_record_at[t] = (uint32_t)(records + 4 * (size_t)t);
+            std::memcpy(reinterpret_cast<uint8_t*>(uvs.data() + tex_record_at[t]), &r, sizeof(r));
+        }
+        // Image environment maps: the CDF of each (host/env_cdf.h) goes behind the texels
+        for (uint32_t l = 0; l < desc.num_lights; ++l) {
+            const igx_light& L = desc.lights[l];
+            if (L.type != IGX_LIGHT_ENVMAP) continue;
+            const igx_texture& tx = desc.textures[L.env_texture];
+            const igx_image& im = desc.images[tx.image];
+            EnvMap e{};
+            static_assert(offsetof(DevLight, radiance) == 16 && sizeof(DevLight) == 16 + sizeof(EnvMap), "EnvMap lives behind the DevLight header");
+            for (int i = 0; i < 3; ++i) e.scale[i] = L.env_scale[i];
+            for (int i = 0; i < 9; ++i) e.m[i] = L.sky_transform[i];
+            for (int i = 0; i < 6; ++i) e.uv_transform[i] = tx.transform[i];
+            e.texture = tex_record_at[L.env_texture];
+            if (L.env_cdf && (im.width > 1 || im.height > 1)) {
+                int bw = 0, bh = 0;
+                std::vector<float> baked, table;
+                bake_env_image(tx, im, bw, bh, baked);
+                build_env_cdf(baked.data(), bw, bh, true, L.env_compensate != 0, table);
+                pad_to(2);
+                if (uvs.size() + (table.size() + 1) / 2 > 0x7fffffffu) return fail(IGX_ERR_UNSUPPORTED, "texture coordinates and images exceed 16 GB");
+                e.cdf = (uint32_t)uvs.size();
+                e.cdf_w = bw;
+                e.cdf_h = bh;
+                uvs.resize(uvs.size() + (table.size() + 1) / 2, Float2{0, 0});
+                std::memcpy(reinterpret_cast<uint8_t*>(uvs.data() + e.cdf), table.data(), table.size() * sizeof(float));
+                out.cdf_bytes += table.size() * sizeof(float);
+            }
+            std::memcpy(lights[light_remap[l]].radiance, &e, sizeof(e));
+        }
+    }
     auto& mats = out.mats;
     mats.resize(desc.num_materials);
     for (uint32_t i = 0; i < desc.num_materials; ++i) {
@@ -613,6 +691,13 @@ igx_status build_scene_tables(const igx_scene_desc& desc, const SceneBuildOption
             std::memcpy(&d.pad[0], &kind, 4);
             d.pad[1] = m.tex_scale;
             for (int c = 0; c < 3; ++c) d.pad[2 + c] = m.tex_kd1[c];
+        } else if (m.texture == IGX_TEXTURE_IMAGE && (m.bsdf_type == IGX_BSDF_DIFFUSE || m.bsdf_type == IGX_BSDF_PRINCIPLED)) {
+            if (m.tex_index < 0 || (uint32_t)m.tex_index >= desc.num_textures)
+                return fail(IGX_ERR_INVALID_ARGUMENT, "material " + std::to_string(i) + ": texture index beyond the texture table");
+            const int32_t kind = IGX_TEXTURE_IMAGE;
+            std::memcpy(&d.pad[0], &kind, 4);
+            for (int k = 0; k < 6; ++k) d.pad[1 + k] = desc.textures[m.tex_index].transform[k];
+            std::memcpy(&d.pad[7], &tex_record_at[m.tex_index], 4);
         } else if (m.texture != IGX_TEXTURE_NONE) {
             return fail(IGX_ERR_UNSUPPORTED, "texture " + std::to_string(m.texture) + " on this bsdf type");
         }
@@ -637,6 +722,7 @@ igx_status build_scene_tables(const igx_scene_desc& desc, const SceneBuildOption
             q.eta[1] = m.clearcoat;
             q.eta[2] = m.clearcoat_gloss;
             q.eta[3] = m.clearcoat_roughness;
+            std::memcpy(q.pad, d.pad, sizeof(q.pad)); // an image texture on base_color
             d = q;
         }
         mats[i] = d;
@@ -684,7 +770,7 @@ igx_status build_scene_tables(const igx_scene_desc& desc, const SceneBuildOption
     // and every camera but the pinhole perspective one (gen_pixel), and the CIE skies
     if (camera_needs_full(desc.camera)) out.full_shading = true;
     for (uint32_t l = 0; l < desc.num_lights; ++l)
-        if (desc.lights[l].type == IGX_LIGHT_CIE) out.full_shading = true;
+        if (desc.lights[l].type == IGX_LIGHT_CIE || desc.lights[l].type == IGX_LIGHT_ENVMAP) out.full_shading = true;
     for (uint32_t e = 0; textured && e < desc.num_entities; ++e) {
         const igx_entity& en = desc.entities[e];
         if (desc.materials[en.material].texture != IGX_TEXTURE_NONE && desc.shapes[en.shape].type == IGX_SHAPE_SPHERE)

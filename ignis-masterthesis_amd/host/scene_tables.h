@@ -11,6 +11,7 @@
 
 #include "bvh_build.h"
 #include "device_scene.h"
+#include "image_texture.h"
 #include "light_select.h"
 
 #include <cstddef>
@@ -53,7 +54,8 @@ struct SceneTables {
     std::vector<Float4> ent;     // ENT_STRIDE per entity
     std::vector<Float4> vtx, nrm; // mesh vertices and vertex normals (object space)
     std::vector<Int4> idx;       // faces: local vertex indices
-    std::vector<Float2> uvs;     // texture coordinates, only for scenes with a textured material
+    std::vector<Float2> uvs;     // texture coordinates, only for scenes with a textured material; behind
+                                 // them the image textures' records and texels (igxd::TexRecord)
     std::vector<Float4> fsh;     // per face: vertex normals and indices in one record (SceneView::fsh)
     std::vector<Float4> fn_tab;  // world-space unit face normals (surface_element)
     std::vector<int32_t> ent_fn; // per entity: first face-normal entry, -1 without a table
@@ -75,6 +77,8 @@ struct SceneTables {
     bool full_shading = false;   // the scene needs the full shading variant (variant bit 2)
     bool aov_on = false;         // technique aov_mis
     bool textured = false;       // a material carries a texture
+    size_t image_bytes = 0;      // texels of the image textures in uvs
+    size_t cdf_bytes = 0;        // sampling tables of the image environment maps in uvs
 };
 
 // Build every table of `desc`.  On failure the status and `error` are what

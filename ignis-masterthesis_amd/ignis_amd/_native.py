@@ -43,12 +43,31 @@ class Material(C.Structure):
                 ("specular_tint", C.c_float), ("flatness", C.c_float), ("metallic", C.c_float), ("sheen", C.c_float),
                 ("sheen_tint", C.c_float), ("clearcoat", C.c_float), ("clearcoat_gloss", C.c_float),
                 ("clearcoat_roughness", C.c_float), ("clearcoat_top_only", C.c_int32),
-                ("texture", C.c_int32), ("tex_scale", C.c_float), ("tex_kd1", C.c_float * 3)]
+                ("texture", C.c_int32), ("tex_scale", C.c_float), ("tex_kd1", C.c_float * 3),
+                ("tex_index", C.c_int32)]
+
+
+# igx_material.texture
+TEXTURE_NONE, TEXTURE_CHECKER, TEXTURE_IMAGE = range(3)
+# igx_image.format, igx_texture.filter, igx_texture.wrap_u / wrap_v
+IMAGE_RGBA8, IMAGE_MONO8, IMAGE_FLOAT4 = range(3)
+FILTER_NEAREST, FILTER_BILINEAR, FILTER_BICUBIC = range(3)
+WRAP_REPEAT, WRAP_CLAMP, WRAP_MIRROR = range(3)
+
+
+class Image(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("format", C.c_int32), ("pixels", C.c_void_p)]
+
+
+class Texture(C.Structure):
+    _fields_ = [("image", C.c_int32), ("filter", C.c_int32), ("wrap_u", C.c_int32), ("wrap_v", C.c_int32),
+                ("transform", C.c_float * 6)]
 
 
 # igx_light.type (include/igx_scene.h)
 LIGHT_PLANE, LIGHT_ENV, LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL, LIGHT_SUN, LIGHT_SPHERE, LIGHT_MESH = range(1, 9)
 LIGHT_CIE = 9
+LIGHT_ENVMAP = 10
 # igx_light.sky_kind
 SKY_UNIFORM, SKY_CLOUDY, SKY_CLEAR, SKY_INTERMEDIATE = range(4)
 # igx_camera.type
@@ -64,7 +83,9 @@ class Light(C.Structure):
                 ("sky_kind", C.c_int32), ("has_ground", C.c_int32), ("sky_zenith", C.c_float * 3),
                 ("sky_ground", C.c_float * 3), ("sky_scale", C.c_float * 3), ("ground_brightness", C.c_float),
                 ("sun_direction", C.c_float * 3), ("zenith_ratio", C.c_float), ("sky_c2", C.c_float),
-                ("sky_transform", C.c_float * 9)]
+                ("sky_transform", C.c_float * 9),
+                ("env_texture", C.c_int32), ("env_scale", C.c_float * 3), ("env_cdf", C.c_int32),
+                ("env_compensate", C.c_int32)]
 
 
 class Camera(C.Structure):
@@ -87,7 +108,9 @@ class SceneDesc(C.Structure):
                 ("num_entities", C.c_uint32), ("entities", C.POINTER(Entity)),
                 ("num_materials", C.c_uint32), ("materials", C.POINTER(Material)),
                 ("num_lights", C.c_uint32), ("lights", C.POINTER(Light)),
-                ("scene_bbox_min", C.c_float * 3), ("scene_bbox_max", C.c_float * 3)]
+                ("scene_bbox_min", C.c_float * 3), ("scene_bbox_max", C.c_float * 3),
+                ("num_images", C.c_uint32), ("images", C.POINTER(Image)),
+                ("num_textures", C.c_uint32), ("textures", C.POINTER(Texture))]
 
 
 class LookupEntry(C.Structure):
@@ -108,7 +131,9 @@ class DatabaseView(C.Structure):
 class ShadingView(C.Structure):
     _fields_ = [("film_width", C.c_int32), ("film_height", C.c_int32), ("camera", Camera), ("technique", Technique),
                 ("num_materials", C.c_uint32), ("materials", C.POINTER(Material)),
-                ("num_lights", C.c_uint32), ("lights", C.POINTER(Light))]
+                ("num_lights", C.c_uint32), ("lights", C.POINTER(Light)),
+                ("num_images", C.c_uint32), ("images", C.POINTER(Image)),
+                ("num_textures", C.c_uint32), ("textures", C.POINTER(Texture))]
 
 
 # ---- igx.h ----------------------------------------------------------------
@@ -148,7 +173,7 @@ class Stats(C.Structure):
                 ("hot_node_visits", C.c_uint64 * 3), ("extend_class_shade_cycles", C.c_uint64 * 16),
                 ("shadow_class_rays", C.c_uint64 * 2),
                 ("lds_shading_bytes", C.c_int32), ("extend_block_threads", C.c_int32),
-                ("launches_extend_shaped", C.c_uint64 * 2)]
+                ("launches_extend_shaped", C.c_uint64 * 2), ("image_bytes", C.c_uint64), ("cdf_bytes", C.c_uint64)]
 
     def as_dict(self):
         return {name: (list(getattr(self, name)) if isinstance(getattr(self, name), C.Array) else getattr(self, name))

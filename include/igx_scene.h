@@ -111,9 +111,37 @@ typedef struct igx_material {
     int32_t texture;
     float tex_scale;
     float tex_kd1[3];
+    /* IGX_TEXTURE_IMAGE: kd (diffuse reflectance, principled base_color) is the
+     * image texture `tex_index` of igx_scene_desc::textures at the surface's
+     * texture coordinates; -1 (or 0 with another `texture`) otherwise */
+    int32_t tex_index;
 } igx_material;
 
-enum { IGX_TEXTURE_NONE = 0, IGX_TEXTURE_CHECKER = 1 };
+enum { IGX_TEXTURE_NONE = 0, IGX_TEXTURE_CHECKER = 1, IGX_TEXTURE_IMAGE = 2 };
+
+/* ---- images and image textures ------------------------------------------ */
+/* A decoded image with the reference's semantics (Image.cpp): row 0 is the
+ * file's bottom row.  RGBA8 and MONO8 are its "packed" 8-bit images
+ * (Image::loadPacked: colour bytes already through byte_color_to_linear unless
+ * the texture says `linear`; R in the low byte of each 32-bit texel), unpacked
+ * on the device by / 255 (driver/image.art:9-16); FLOAT4 is a float RGBA image
+ * (EXR, HDR). */
+enum { IGX_IMAGE_RGBA8 = 0, IGX_IMAGE_MONO8 = 1, IGX_IMAGE_FLOAT4 = 2 };
+typedef struct igx_image {
+    int32_t width, height;
+    int32_t format;        /* IGX_IMAGE_* */
+    const void* pixels;    /* width * height texels of 4, 1 or 16 bytes */
+} igx_image;
+
+/* The "image" texture (pattern/ImagePattern.cpp:19-52; texture/image.art) */
+enum { IGX_FILTER_NEAREST = 0, IGX_FILTER_BILINEAR = 1, IGX_FILTER_BICUBIC = 2 };
+enum { IGX_WRAP_REPEAT = 0, IGX_WRAP_CLAMP = 1, IGX_WRAP_MIRROR = 2 };
+typedef struct igx_texture {
+    int32_t image;         /* index into igx_scene_desc::images */
+    int32_t filter;        /* IGX_FILTER_*, "filter_type", default bicubic */
+    int32_t wrap_u, wrap_v;/* IGX_WRAP_*, "wrap_mode" or "wrap_mode_u" / "wrap_mode_v", default repeat */
+    float transform[6];    /* 2x3 row-major: uv' = transform * (u, v, 1) (LoaderUtils::inlineTransformAs2d) */
+} igx_texture;
 
 /* ---- lights ------------------------------------------------------------ */
 enum {
@@ -125,7 +153,9 @@ enum {
     IGX_LIGHT_SUN   = 6, /* light/sun.art:4-30 (delta, infinite) */
     IGX_LIGHT_SPHERE = 7, /* area light on a (near-)spherical entity: make_sphere_area_emitter (light/area.art:240-293) */
     IGX_LIGHT_MESH  = 8, /* area light on any triangle entity: make_shape_area_emitter (light/area.art:45-105) */
-    IGX_LIGHT_CIE   = 9  /* analytic CIE sky: make_cie_sky_light / make_cie_sunny_light (light/cie.art:9-42) */
+    IGX_LIGHT_CIE   = 9, /* analytic CIE sky: make_cie_sky_light / make_cie_sunny_light (light/cie.art:9-42) */
+    IGX_LIGHT_ENVMAP = 10 /* image environment map: make_environment_light_textured, or make_environment_light
+                             without a CDF (light/env.art:112-164) */
 };
 /* igx_light.sky_kind (CIELight.h CIEType; LoaderLight.cpp:90-97) */
 enum { IGX_SKY_UNIFORM = 0, IGX_SKY_CLOUDY = 1, IGX_SKY_CLEAR = 2, IGX_SKY_INTERMEDIATE = 3 };
@@ -160,6 +190,16 @@ typedef struct igx_light {
     float zenith_ratio;    /* zenith brightness / factor (clear / intermediate) */
     float sky_c2;          /* ground term of the clear / intermediate sky */
     float sky_transform[9];/* transform.linear().transpose().inverse(), row-major */
+    /* IGX_LIGHT_ENVMAP (EnvironmentLight.cpp:10-74); zero for every other type.
+     * The radiance in direction d is env_scale * texture(map_env_uv(sky_transform * d)),
+     * the map Y-up in its own frame.  With env_cdf (property "cdf", default true)
+     * and an image larger than 1 x 1 the light is sampled through a 2-D CDF built at
+     * upload on a bake of the texture ("compensate", default true: MIS
+     * compensation); otherwise uniformly over the sphere.  Both the sampled and
+     * the seen radiance carry env_scale ("Image textures"). */
+    int32_t env_texture;   /* index into igx_scene_desc::textures */
+    float env_scale[3];
+    int32_t env_cdf, env_compensate;
 } igx_light;
 
 /* ---- camera / technique ------------------------------------------------ */
@@ -205,6 +245,8 @@ typedef struct igx_scene_desc {
     uint32_t num_materials; const igx_material* materials;
     uint32_t num_lights;    const igx_light* lights;
     float scene_bbox_min[3], scene_bbox_max[3];
+    uint32_t num_images;    const igx_image* images;
+    uint32_t num_textures;  const igx_texture* textures;
 } igx_scene_desc;
 
 /* ---- loader C-ABI (stand-in for the reference's Loader, src/runtime/loader) */
@@ -326,6 +368,15 @@ typedef struct igx_shading_view {
     igx_technique technique;
     uint32_t num_materials; const igx_material* materials;
     uint32_t num_lights;    const igx_light* lights;
+    /* image textures of the materials (igx_material::tex_index) and the
+     * environment maps (igx_light::env_texture); igx_scene_from_database copies
+     * the pixels.  A caller that keeps a view and hands it over again (the
+     * IG::Device facade, host/Device.h) is taken to have changed an image only
+     * if its size, format or `pixels` address changed: texels rewritten in
+     * place behind the same address are not looked at, so give a changed image
+     * a new buffer. */
+    uint32_t num_images;    const igx_image* images;
+    uint32_t num_textures;  const igx_texture* textures;
 } igx_shading_view;
 
 /* Build a scene from the reference's tables plus the shading view.  Plane
