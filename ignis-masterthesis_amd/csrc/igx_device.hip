@@ -347,6 +347,56 @@ __device__ __forceinline__ void wave_append_paths(bool alive, int cls, bool shad
                      : a0 + __popcll(ma & below);
     sdst = sh_b ? sh_cap - 1 - (t0 + __popcll(sb & below)) : s0 + __popcll(sa & below);
 }
+// wave_append_paths in two halves (k_extend's generate and bounce shapes): the
+// first issues the one returning atomic (counters and claim), the second
+// turns its results into the lanes' positions.  The compiled kernel waits
+// for the atomic right behind it (the radiance sum needs the load issued
+// ahead of it, and a load and an atomic under lane branches are waited for
+// together), so nothing overlaps the round trip but the load.  Same counters,
+// same counts, same positions as wave_append_paths.
+struct AppendIssued {
+    uint64_t ma, mb, mc, sa, sb; // ballots: path classes A, B, C, shadow classes A, B
+    unsigned long long r;        // lanes 0-2: the counters' previous values, lane 3: the claimed group
+};
+__device__ __forceinline__ AppendIssued wave_append_issue(bool alive, int cls, bool shadow, bool sh_b, int* cp, int* cs, int* claim) {
+    const int lane = lane_id();
+    AppendIssued t;
+    t.ma = __ballot(alive && cls == 0), t.mb = __ballot(alive && cls == 1), t.mc = __ballot(alive && cls == 2);
+    t.sa = __ballot(shadow && !sh_b), t.sb = __ballot(shadow && sh_b);
+    // lane 3 takes the next group in the same instruction: a 64-bit add of 1
+    // to the shard's work counter, whose line holds nothing else (its upper
+    // word stays 0: the rows are cleared per chunk and a counter stays far
+    // below 2^32), so the lower word of the result is what atomicAdd(claim, 1)
+    // returns.  One returning atomic per group, and none whose result the
+    // compiler's wave-level rewrite of a uniform atomic would need at once.
+    const unsigned long long want = lane == 0   ? ((unsigned long long)__popcll(t.ma) | ((unsigned long long)__popcll(t.mb) << 32))
+                                    : lane == 1 ? ((unsigned long long)__popcll(t.sa) | ((unsigned long long)__popcll(t.sb) << 32))
+                                    : lane == 2 ? (unsigned long long)__popcll(t.mc)
+                                                : (claim ? 1ull : 0ull);
+    t.r = 0;
+    if (lane < 4 && want != 0)
+        t.r = atomicAdd(reinterpret_cast<unsigned long long*>(lane == 0 ? cp : lane == 1 ? cs : lane == 2 ? cp + 2 : claim), want);
+    return t;
+}
+__device__ __forceinline__ void wave_append_finish(const AppendIssued& t, int cls, bool sh_b, int shard_cap, int c_base, int sh_cap,
+                                                   int& dst, int& sdst, bool claim, int& claimed) {
+    const uint64_t below = (1ull << lane_id()) - 1ull;
+    const int lo = (int)(uint32_t)t.r, hi = (int)(uint32_t)(t.r >> 32);
+    claimed = claim ? __builtin_amdgcn_readfirstlane(__shfl(lo, 3)) : -1;
+    const int a0 = __shfl(lo, 0), b0 = __shfl(hi, 0), s0 = __shfl(lo, 1), t0 = __shfl(hi, 1), c0 = __shfl(lo, 2);
+    dst = cls == 1   ? shard_cap - 1 - (b0 + __popcll(t.mb & below))
+          : cls == 2 ? c_base + c0 + __popcll(t.mc & below)
+                     : a0 + __popcll(t.ma & below);
+    sdst = sh_b ? sh_cap - 1 - (t0 + __popcll(t.sb & below)) : s0 + __popcll(t.sa & below);
+}
+// Record at byte offset `off` of an array whose base is wave-uniform (the
+// shapes: every array of a stream is at most 4 GiB, streams_offsets_32bit of
+// host/extend_shape.h, so a lane's address is the scalar base plus a 32-bit
+// offset and needs no 64-bit arithmetic per lane)
+template <class T>
+__device__ __forceinline__ T* rec_at(T* base, uint32_t off) {
+    return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off);
+}
 
 
 
@@ -542,6 +592,40 @@ __device__ __forceinline__ int path_class(int classify, const SceneView& sv, con
     case 4: return ps.eta != 1.0f ? 2 : crosses_enclosing_box(sv, ps.o, ps.d);
     default: return 0;
     }
+}
+
+// crosses_enclosing_box of the bounced ray (direction pd, lanes `test_p`) and
+// shadow_class_b of the shadow ray (direction sd, segment [0, stmax], lanes
+// `test_s`) in one pass over the enclosing boxes, without a branch per lane
+// (k_extend's shapes): both rays leave the same point o, so a box is read
+// once and its origin-relative corners serve both slab tests, and a ray's
+// result is the OR over the boxes where the two loops leave at the first
+// hit.  Per ray the float operations are those of the two predicates, in
+// their order, so every ray gets the class it gets there.  A wave with no
+// lane to test skips the pass by a scalar branch.
+__device__ __forceinline__ void class_pass(const SceneView& sv, f3 o, bool test_p, f3 pd, bool test_s, f3 sd, float stmax,
+                                           bool& p_hit, bool& s_hit) {
+    p_hit = s_hit = false;
+    if (sv.num_enc <= 0 || !__ballot(test_p || test_s)) return;
+    const f3 ip = fast_rcp3(pd), is = fast_rcp3(sd);
+    for (int k = 0; k < sv.num_enc; ++k) {
+        const float4 lo = sv.enc_box[2 * k], hi = sv.enc_box[2 * k + 1];
+        const float lx = lo.x - o.x, hx = hi.x - o.x, ly = lo.y - o.y, hy = hi.y - o.y, lz = lo.z - o.z, hz = hi.z - o.z;
+        {
+            const float ax = lx * ip.x, bx = hx * ip.x, ay = ly * ip.y, by = hy * ip.y, az = lz * ip.z, bz = hz * ip.z;
+            const float en = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
+            const float ex = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+            p_hit |= en <= ex && ex >= 0.0f;
+        }
+        {
+            const float ax = lx * is.x, bx = hx * is.x, ay = ly * is.y, by = hy * is.y, az = lz * is.z, bz = hz * is.z;
+            const float en = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
+            const float ex = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+            s_hit |= en <= ex && ex >= 0.0f && en <= stmax;
+        }
+    }
+    p_hit = p_hit && test_p;
+    s_hit = s_hit && test_s;
 }
 
 __device__ __forceinline__ PathState path_from_records(float4 p0, float4 p1, float4 p2, float2 p3) {
@@ -802,6 +886,13 @@ __device__ __forceinline__ void phase_mark(TraceStats& st, unsigned long long& l
     st.cyc[k] += now - last;
     last = now;
 }
+// a mark inside the store phase (3): the cycles also go to part `part` of
+// TraceStats::store_part (0 group take, 1 class tests, 2 append, 3 stores)
+__device__ __forceinline__ void store_mark(TraceStats& st, unsigned long long& last, int part) {
+    const unsigned long long c = st.cyc[3];
+    phase_mark(st, last, 3);
+    st.store_part[part] += st.cyc[3] - c;
+}
 template <bool STATS, int V>
 __device__ __forceinline__ bool extend_step(const FrameArgs& fa, const SceneView& sv, const TStack& ts, PathState& ps, f3& Lacc,
                                             bool& has_l, bool& has_shadow, ShadowRec& sr, TraceStats& st) {
@@ -918,6 +1009,7 @@ __device__ __forceinline__ void flush_stats(const TraceStats& st, unsigned long 
         }
         if (st.cyc[0] | st.cyc[1] | st.cyc[2] | st.cyc[3]) {
             for (int k = 0; k < 4; ++k) atomicAdd(&stats[16 + k], st.cyc[k]);
+            for (int k = 0; k < 4; ++k) atomicAdd(&stats[72 + k], st.store_part[k]); // the store phase by part
             if (st.cls)
                 for (int k = 0; k < 20; ++k)
                     if (st.cls[k]) atomicAdd(&stats[20 + k], st.cls[k]);
@@ -1021,20 +1113,22 @@ __global__ void __launch_bounds__(BT, LDS ? EXTEND_WAVES_LDS : (variant_full(V0)
         // streams_packed): both path buffers and the shadow stream share the
         // shard capacity, a path buffer holds the class-C region behind its
         // shards, and the three counter rows of a bounce are neighbours
+        // (the arrays' byte offsets: stream_layout, host/extend_shape.h)
         const int cap = out.shard_cap;
-        const size_t recs = (size_t)NSH * cap;
+        const StreamLayout lay = stream_layout(cap);
+        auto at = [](float4* base, unsigned long long off) { return reinterpret_cast<float4*>(reinterpret_cast<char*>(base) + off); };
         auto derive = [&](PathBuf& b) {
             b.shard_cap = cap;
             b.c_base = NSH * cap;
-            b.p1 = b.p0 + 2 * recs;
-            b.p2 = b.p0 + 4 * recs;
-            b.p3 = reinterpret_cast<float2*>(b.p0 + 6 * recs);
+            b.p1 = at(b.p0, lay.p_off[1]);
+            b.p2 = at(b.p0, lay.p_off[2]);
+            b.p3 = reinterpret_cast<float2*>(at(b.p0, lay.p_off[3]));
         };
         derive(out);
         if constexpr (SHAPE == EXTEND_BOUNCE) derive(in);
         sh.shard_cap = cap;
-        sh.s1 = sh.s0 + recs;
-        sh.s2 = sh.s0 + 2 * recs;
+        sh.s1 = at(sh.s0, lay.s_off[1]);
+        sh.s2 = at(sh.s0, lay.s_off[2]);
         kc.cnt_shadow = kc.cnt_in + CROW;
         kc.cnt_out = kc.cnt_in + 2 * CROW;
     }
@@ -1086,7 +1180,7 @@ __global__ void __launch_bounds__(BT, LDS ? EXTEND_WAVES_LDS : (variant_full(V0)
         } else if (p0 >= sc.n) {
             break;
         }
-        if (STATS) phase_mark(st, t_last, 3); // group distribution
+        if constexpr (STATS) store_mark(st, t_last, 0); // group distribution
         const int ns = sc.n;
         int* const c_out = kc.cnt_out + s * CSTRIDE;
         int* const c_sh = kc.cnt_shadow + s * CSTRIDE;
@@ -1102,6 +1196,10 @@ __global__ void __launch_bounds__(BT, LDS ? EXTEND_WAVES_LDS : (variant_full(V0)
                 const int i = ((pos >> 6) << 12) | (s << 6) | (pos & 63);
                 ps = camera_path<variant_full(V0)>(fa, sv, i);
                 if (variant_full(V0) && IGX_AOV && fa.aov_di) fa.aov_di[i] = fa.aov_nee[i] = make_float4(0, 0, 0, 0);
+            } else if constexpr (SHAPE != EXTEND_GENERIC) { // load_path by scalar bases (rec_at)
+                const uint32_t i = (uint32_t)path_index(in, s, pos, sc);
+                ps = path_from_records(*rec_at(in.p0, i * (uint32_t)sizeof(float4)), *rec_at(in.p1, i * (uint32_t)sizeof(float4)),
+                                       *rec_at(in.p2, i * (uint32_t)sizeof(float4)), *rec_at(in.p3, i * (uint32_t)sizeof(float2)));
             } else {
                 ps = load_path(in, path_index(in, s, pos, sc));
             }
@@ -1113,48 +1211,111 @@ __global__ void __launch_bounds__(BT, LDS ? EXTEND_WAVES_LDS : (variant_full(V0)
             const int bucket = gen ? 0 : (pg < sc.a ? 1 : pg < sc.ab ? 2 : 3);
             alive = extend_step_instrumented<V>(fa, sv, ts, ps, q < ns && ps.depth > 0, bucket, Lacc, has_l, has_shadow, sr, st, t_last);
         }
-        const bool sh_b = has_shadow && shadow_class_b(fa.shadow_classes, sv, sr.o, sr.d, sr.tmax);
-        // The path's radiance slot takes the emission (has_l) and, with
-        // shadow_optimistic, the colour of a class-A shadow ray in one
-        // read-modify-write: the shadow kernel adds nothing for such a ray and
-        // puts `undo` back if it is occluded (ShadowBuf::s2).  A generated path
-        // (bounce 0) starts from +0 in registers and writes its slot once, dead
-        // and padding paths included (k_generate's zero fill).  The scattered
-        // load goes out ahead of the append's returning atomic and is consumed
-        // behind it: one round trip for both.
-        const bool opt_add = fa.shadow_optimistic && has_shadow && !sh_b;
-        const bool upd = gen ? q < ns : (has_l || opt_add);
-        float4 l = make_float4(0, 0, 0, 0);
-        if (!gen && upd) l = L[ps.slot];
-        int dst, sdst;
-        // dynamic groups: the append's round trip also takes the next group of
-        // shard s, unless s is known exhausted
-        int* const claim = (IGX_CLAIM_NEXT && fa.dynamic && !((done >> s) & 1ull)) ? kc.work + s * CSTRIDE : nullptr;
-        wave_append_paths(alive, path_class(fa.classify, sv, ps), has_shadow, sh_b, c_out, c_sh, out.shard_cap,
-                          out.c_base, sh.shard_cap, dst, sdst, claim, &claimed);
-        if (!claim) claimed = -1;
-        if (alive) store_path(out, s * out.shard_cap + dst, ps);
-        f3 rec = sr.color; // the shadow record's third word
-        if (upd) {
+        if constexpr (SHAPE != EXTEND_GENERIC) {
+            // The store phase of the shapes writes what the generic kernel's
+            // (the other branch, where the steps are described) writes, record
+            // for record: both class tests in one pass over the enclosing boxes
+            // (class_pass), one returning atomic for the append and the claim,
+            // issued as soon as the classes are known (wave_append_issue), and
+            // every record addressed as a wave-uniform array base plus a 32-bit
+            // byte offset (rec_at).
+            // The radiance load goes out first, under no branch and ahead of
+            // the class pass, for every lane that may update its slot (a lane
+            // that then does not drops the value; the others read slot 0): the
+            // compiler waits for a load issued under a branch at the branch's
+            // end, so the generic kernel's load and its atomics are two round
+            // trips in a row; here the load, the class pass and the atomic
+            // overlap and one wait behind the atomic serves both.
+            // (a lane past the group's end, q >= ns, holds no path: its ps.slot
+            // is undefined, has_l and has_shadow are false there, so it reads
+            // slot 0 and stores nothing; a slot index has SLOT_BITS bits, so the
+            // byte offset into L fits 32 bits)
+            static_assert(SLOT_BITS + 4 <= 32, "a radiance slot's byte offset fits 32 bits");
+            const uint32_t l_off = (uint32_t)ps.slot * (uint32_t)sizeof(float4);
+            float4 l = make_float4(0, 0, 0, 0);
+            if constexpr (SHAPE == EXTEND_BOUNCE) l = *rec_at(L, (has_l || (fa.shadow_optimistic && has_shadow)) ? l_off : 0u);
+            bool p_b, sh_b;
+            class_pass(sv, has_shadow ? sr.o : ps.o, alive && ps.eta == 1.0f, ps.d, has_shadow, sr.d, sr.tmax, p_b, sh_b);
+            const int cls = ps.eta != 1.0f ? 2 : (int)p_b; // path_class, FrameArgs::classify 4
+            const bool opt_add = fa.shadow_optimistic && has_shadow && !sh_b;
+            const bool upd = gen ? q < ns : (has_l || opt_add);
+            int* const claim = (IGX_CLAIM_NEXT && !((done >> s) & 1ull)) ? kc.work + s * CSTRIDE : nullptr;
+            const AppendIssued ap = wave_append_issue(alive, cls, has_shadow, sh_b, c_out, c_sh, claim);
+            const float w_slot = __uint_as_float((uint32_t)ps.slot | ((uint32_t)(ps.inside + 1) << SLOT_BITS));
+            const float w_count = __uint_as_float(ps.counter | ((uint32_t)ps.depth << 24));
+            f3 rec = sr.color; // the shadow record's third word
             f3 v = f3of(l);
-            if (has_l) {
-                v = mk(v.x + Lacc.x, v.y + Lacc.y, v.z + Lacc.z); // add_radiance
-                add_aov<variant_full(V0)>(fa.aov_di, ps.slot, Lacc);
-            }
+            if (has_l) v = mk(v.x + Lacc.x, v.y + Lacc.y, v.z + Lacc.z); // add_radiance
             if (opt_add) {
                 rec = v; // undo
                 v = mk(v.x + sr.color.x, v.y + sr.color.y, v.z + sr.color.z);
             }
-            L[ps.slot] = make_float4(v.x, v.y, v.z, 0);
+            int dst, sdst;
+            wave_append_finish(ap, cls, sh_b, out.shard_cap, out.c_base, sh.shard_cap, dst, sdst, claim != nullptr, claimed);
+            if (alive) {
+                const uint32_t e = (uint32_t)(s * out.shard_cap + dst);
+                *rec_at(out.p0, e * (uint32_t)sizeof(float4)) = make_float4(ps.o.x, ps.o.y, ps.o.z, w_slot);
+                *rec_at(out.p1, e * (uint32_t)sizeof(float4)) = make_float4(ps.d.x, ps.d.y, ps.d.z, w_count);
+                *rec_at(out.p2, e * (uint32_t)sizeof(float4)) = make_float4(ps.contrib.x, ps.contrib.y, ps.contrib.z, ps.inv_pdf);
+                *rec_at(out.p3, e * (uint32_t)sizeof(float2)) = make_float2(ps.eta, __uint_as_float(ps.seed));
+            }
+            if (upd) *rec_at(L, l_off) = make_float4(v.x, v.y, v.z, 0);
+            if (has_shadow) {
+                const uint32_t e = (uint32_t)(s * sh.shard_cap + sdst) * (uint32_t)sizeof(float4);
+                *rec_at(sh.s0, e) = make_float4(sr.o.x, sr.o.y, sr.o.z, __int_as_float(ps.slot));
+                *rec_at(sh.s1, e) = make_float4(sr.d.x, sr.d.y, sr.d.z, sr.tmax);
+                *rec_at(sh.s2, e) = make_float4(rec.x, rec.y, rec.z, 0);
+            }
+        } else {
+            const bool sh_b = has_shadow && shadow_class_b(fa.shadow_classes, sv, sr.o, sr.d, sr.tmax);
+            int cls_marked = 0; // instrumented: the path class, taken ahead of the append for the class-test clock
+            if constexpr (STATS) {
+                cls_marked = path_class(fa.classify, sv, ps);
+                store_mark(st, t_last, 1);
+            }
+            // The path's radiance slot takes the emission (has_l) and, with
+            // shadow_optimistic, the colour of a class-A shadow ray in one
+            // read-modify-write: the shadow kernel adds nothing for such a ray and
+            // puts `undo` back if it is occluded (ShadowBuf::s2).  A generated path
+            // (bounce 0) starts from +0 in registers and writes its slot once, dead
+            // and padding paths included (k_generate's zero fill).  The scattered
+            // load goes out ahead of the append's returning atomic and is consumed
+            // behind it: one round trip for both.
+            const bool opt_add = fa.shadow_optimistic && has_shadow && !sh_b;
+            const bool upd = gen ? q < ns : (has_l || opt_add);
+            float4 l = make_float4(0, 0, 0, 0);
+            if (!gen && upd) l = L[ps.slot];
+            int dst, sdst;
+            // dynamic groups: the append's round trip also takes the next group of
+            // shard s, unless s is known exhausted
+            int* const claim = (IGX_CLAIM_NEXT && fa.dynamic && !((done >> s) & 1ull)) ? kc.work + s * CSTRIDE : nullptr;
+            wave_append_paths(alive, STATS ? cls_marked : path_class(fa.classify, sv, ps), has_shadow, sh_b, c_out, c_sh, out.shard_cap,
+                              out.c_base, sh.shard_cap, dst, sdst, claim, &claimed);
+            if (!claim) claimed = -1;
+            if constexpr (STATS) store_mark(st, t_last, 2); // radiance load and append round trip
+            if (alive) store_path(out, s * out.shard_cap + dst, ps);
+            f3 rec = sr.color; // the shadow record's third word
+            if (upd) {
+                f3 v = f3of(l);
+                if (has_l) {
+                    v = mk(v.x + Lacc.x, v.y + Lacc.y, v.z + Lacc.z); // add_radiance
+                    add_aov<variant_full(V0)>(fa.aov_di, ps.slot, Lacc);
+                }
+                if (opt_add) {
+                    rec = v; // undo
+                    v = mk(v.x + sr.color.x, v.y + sr.color.y, v.z + sr.color.z);
+                }
+                L[ps.slot] = make_float4(v.x, v.y, v.z, 0);
+            }
+            if (has_shadow) {
+                const int e = s * sh.shard_cap + sdst;
+                sh.s0[e] = make_float4(sr.o.x, sr.o.y, sr.o.z, __int_as_float(ps.slot));
+                sh.s1[e] = make_float4(sr.d.x, sr.d.y, sr.d.z, sr.tmax);
+                sh.s2[e] = make_float4(rec.x, rec.y, rec.z, 0);
+            }
+            if (!fa.dynamic) p0 += w.K * 64;
+            if constexpr (STATS) store_mark(st, t_last, 3); // stores
         }
-        if (has_shadow) {
-            const int e = s * sh.shard_cap + sdst;
-            sh.s0[e] = make_float4(sr.o.x, sr.o.y, sr.o.z, __int_as_float(ps.slot));
-            sh.s1[e] = make_float4(sr.d.x, sr.d.y, sr.d.z, sr.tmax);
-            sh.s2[e] = make_float4(rec.x, rec.y, rec.z, 0);
-        }
-        if (!fa.dynamic) p0 += w.K * 64;
-        if (STATS) phase_mark(st, t_last, 3);
     }
     if (STATS) flush_stats<STATS>(st, kc.stats, 0, true);
 }
@@ -2062,7 +2223,8 @@ constexpr int WORK_ROW0 = 2 * MAX_BOUNCES + 4;
 // instrumentation counters (igx_get_stats): 0-12 visit counts, 16-19 k_extend
 // phase clocks, 20-39 k_extend by group class, 40-49 k_shadow by class, 50-53
 // closest-hit node visits in the TLAS and by hot-order rank, 54-69 k_extend
-// shading sub-phase clocks by class, 70-71 k_shadow rays by class
+// shading sub-phase clocks by class, 70-71 k_shadow rays by class, 72-75 k_extend
+// store phase by part (igx_get_store_split)
 [[maybe_unused]] constexpr int DSTATS = 80;
 constexpr int CTR_ROWS = WORK_ROW0 + 4 * MAX_BOUNCES;
 [[maybe_unused]] constexpr size_t CTR_INTS = (size_t)CTR_ROWS * CROW;
@@ -2644,14 +2806,20 @@ inline ExtendShape launch_shape(const igx_device* dev, bool instrumented, const 
     in.num_rays = fa.num_rays;
     in.mis_aovs = fa.aov_di != nullptr || fa.aov_nee != nullptr;
     // the layout the shapes derive their pointers from (k_extend)
-    const auto packed = [&](const PathBuf& b) {
-        const size_t recs = (size_t)NSH * b.shard_cap;
-        return b.shard_cap == out.shard_cap && b.c_base == NSH * b.shard_cap && b.p1 == b.p0 + 2 * recs && b.p2 == b.p0 + 4 * recs &&
-               b.p3 == reinterpret_cast<const float2*>(b.p0 + 6 * recs);
+    // (stream_layout: the offsets k_extend adds to the first pointer of a stream)
+    static_assert(EXTEND_SHARDS == NSH, "stream_layout counts NSH shards");
+    const StreamLayout lay = stream_layout(out.shard_cap);
+    const auto byte_off = [](const void* p, const void* base) {
+        return (unsigned long long)(reinterpret_cast<const char*>(p) - reinterpret_cast<const char*>(base));
     };
-    const size_t srecs = (size_t)NSH * sh.shard_cap;
-    in.streams_packed = packed(pin) && packed(out) && sh.shard_cap == out.shard_cap && sh.s1 == sh.s0 + srecs && sh.s2 == sh.s0 + 2 * srecs &&
-                        kc.cnt_shadow == kc.cnt_in + CROW && kc.cnt_out == kc.cnt_in + 2 * CROW;
+    const auto packed = [&](const PathBuf& b) {
+        return b.shard_cap == out.shard_cap && (unsigned long long)b.c_base == lay.shadow_records && byte_off(b.p1, b.p0) == lay.p_off[1] &&
+               byte_off(b.p2, b.p0) == lay.p_off[2] && byte_off(b.p3, b.p0) == lay.p_off[3];
+    };
+    in.streams_packed = packed(pin) && packed(out) && sh.shard_cap == out.shard_cap && byte_off(sh.s1, sh.s0) == lay.s_off[1] &&
+                        byte_off(sh.s2, sh.s0) == lay.s_off[2] && kc.cnt_shadow == kc.cnt_in + CROW && kc.cnt_out == kc.cnt_in + 2 * CROW;
+    // and reach a record by a 32-bit byte offset from its array's base
+    in.offsets_32bit = streams_offsets_32bit(out.shard_cap);
     return pick_extend_shape(in);
 }
 
@@ -4620,6 +4788,17 @@ extern "C" igx_status igx_get_stats(igx_device* dev, igx_stats* out) {
     for (const Slot& s : dev->slots)
         out->slot_bytes += (uint64_t)s.shard_cap * NSH * (2 * 56 * (s.pa.c_base ? 2 : 1) + 48 + (s.hb.h ? 20 : 0)) +
                            (uint64_t)s.cap * (16 + (s.aov_di ? 32 : 0));
+    return IGX_OK;
+}
+
+extern "C" igx_status igx_get_store_split(igx_device* dev, uint64_t out[4]) {
+    if (!dev || !out) return IGX_ERR_INVALID_ARGUMENT;
+    HIPCHK(hipSetDevice(dev->hip_device));
+    igx_status st = drain(dev);
+    if (st != IGX_OK) return st;
+    unsigned long long h[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(h, dev->dstats + 72, sizeof(h), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 4; ++k) out[k] = h[k];
     return IGX_OK;
 }
 

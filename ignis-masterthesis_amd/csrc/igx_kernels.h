@@ -170,6 +170,9 @@ struct TraceStats {
     uint32_t tlas_nodes = 0, hot[3] = {0, 0, 0};
     // k_extend phase clocks (wave-level, s_memtime): load, trace, shade, store
     unsigned long long cyc[4] = {0, 0, 0, 0};
+    // the store phase's clock (cyc[3]) by part: group take, class tests,
+    // append round trip (with the radiance load ahead of it), stores
+    unsigned long long store_part[4] = {0, 0, 0, 0};
     // k_extend by the class of the wave's group (camera, A, B, C): trace
     // cycles 0-3, shade cycles 4-7, groups 8-11, wave-level node iterations
     // 12-15, lane node visits 16-19 -- the wave's 20 counters in LDS (lane 0

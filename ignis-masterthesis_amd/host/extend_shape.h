@@ -38,7 +38,33 @@ struct ExtendShapeInput {
     // class-C region behind the shards, the shadow stream's likewise, one shard
     // capacity for all, the bounce's three counter rows adjacent
     bool streams_packed = true;
+    // every array of those streams is at most 4 GiB, so the shapes reach a
+    // record by a wave-uniform array base plus a 32-bit byte offset per lane
+    // (streams_offsets_32bit of the launch's shard capacity)
+    bool offsets_32bit = true;
 };
+
+// The arrays of the packed streams of shard capacity `shard_cap` records
+// (NSH shards): byte offsets from the stream's first pointer, and the bytes
+// of one array.  A path buffer holds the class-C region behind its shards
+// (2 * NSH * shard_cap records per array: p0, p1, p2 of 16 B, p3 of 8 B), the
+// shadow stream NSH * shard_cap records per array (s0, s1, s2 of 16 B).
+constexpr int EXTEND_SHARDS = 64; // NSH
+struct StreamLayout {
+    unsigned long long path_records;    // records per path array
+    unsigned long long shadow_records;  // records per shadow array
+    unsigned long long p_off[4];        // p0, p1, p2, p3 from PathBuf::p0, in bytes
+    unsigned long long s_off[3];        // s0, s1, s2 from ShadowBuf::s0, in bytes
+    unsigned long long max_array_bytes; // the largest single array
+};
+constexpr StreamLayout stream_layout(int shard_cap) {
+    const unsigned long long recs = (unsigned long long)EXTEND_SHARDS * (unsigned long long)shard_cap;
+    return StreamLayout{2 * recs, recs, {0, 32 * recs, 64 * recs, 96 * recs}, {0, 16 * recs, 32 * recs}, 32 * recs};
+}
+// the byte offset of the last record of the largest array fits 32 bits
+constexpr bool streams_offsets_32bit(int shard_cap) {
+    return shard_cap >= 0 && stream_layout(shard_cap).max_array_bytes <= (1ull << 32);
+}
 
 // auto (-1) of option "extend_shapes"
 #ifndef EXTEND_SHAPES_AUTO
@@ -48,7 +74,7 @@ struct ExtendShapeInput {
 inline ExtendShape pick_extend_shape(const ExtendShapeInput& in) {
     const int opt = in.extend_shapes < 0 ? EXTEND_SHAPES_AUTO : in.extend_shapes;
     if (opt == 0 || in.instrument) return EXTEND_GENERIC;
-    if (!in.dynamic || in.reverse || in.classify != EXTEND_SHAPE_CLASSIFY || in.shadow_classes != 1 || in.num_rays > 0 || in.mis_aovs || !in.streams_packed)
+    if (!in.dynamic || in.reverse || in.classify != EXTEND_SHAPE_CLASSIFY || in.shadow_classes != 1 || in.num_rays > 0 || in.mis_aovs || !in.streams_packed || !in.offsets_32bit)
         return EXTEND_GENERIC;
     return in.gen_n > 0 ? EXTEND_GENERATE : EXTEND_BOUNCE;
 }

@@ -424,6 +424,13 @@ class Device:
         self._check(self._lib.igx_get_stats(self._h, C.byref(s)))
         return s.as_dict()
 
+    def store_split(self):
+        """igx_get_store_split: the instrumented k_extend's store-phase wave
+        cycles by part (group take, class tests, append, stores)."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._lib.igx_get_store_split(self._h, out))
+        return list(out)
+
     def reset_stats(self):
         self._check(self._lib.igx_reset_stats(self._h))
 

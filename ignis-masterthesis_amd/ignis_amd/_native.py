@@ -208,7 +208,7 @@ EXPORTED_SYMBOLS = [
     "igx_render_iterations", "igx_objscene_create", "igx_objscene_free", "igx_objscene_add",
     "igx_objscene_set_property", "igx_scene_from_objects", "igx_set_camera", "igx_camera_rays",
     "igx_clear_aov", "igx_aov_iteration_count", "igx_write_exr_layers",
-    "igx_tonemap", "igx_imageinfo", "igx_tonemap_film", "igx_imageinfo_film",
+    "igx_tonemap", "igx_imageinfo", "igx_tonemap_film", "igx_imageinfo_film", "igx_get_store_split",
 ]
 
 _lib = None
@@ -276,6 +276,9 @@ def lib():
     L.igx_wait_ready.argtypes = [vp]
     L.igx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.igx_reset_stats.argtypes = [vp]
+    if hasattr(L, "igx_get_store_split"):  # an IGX_LIB_PATH build of an older commit (A/B runs) has none
+        L.igx_get_store_split.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.igx_get_store_split.restype = C.c_int
     L.igx_trace_hits.argtypes = [vp, C.POINTER(C.c_float), C.c_int32, C.c_uint32, C.POINTER(C.c_int32),
                                  C.POINTER(C.c_float)]
     L.igx_trace_occlusion.argtypes = [vp, C.POINTER(C.c_float), C.c_int32, C.c_uint32, C.POINTER(C.c_int32)]

@@ -34,6 +34,11 @@ cyc = [s["extend_cycles_" + k] for k in ("load", "trace", "shade", "store")]
 if sum(cyc):  # share of k_extend's wave time per phase (instrumented build)
     out.update({"ext_phase_" + k: c / sum(cyc) for k, c in zip(("load", "trace", "shade", "store"), cyc)})
     out["ext_wave_cycles/64rays"] = 64 * sum(cyc) / max(1, s["extend_rays"])
+split = dev.store_split() if hasattr(dev._lib, "igx_get_store_split") else [0] * 4  # an older IGX_LIB_PATH library has none
+if sum(split):  # the store phase by part: share of the phase, and of k_extend's wave time
+    for k, c in zip(("take", "class", "append", "stores"), split):
+        out["ext_store_" + k] = c / sum(split)
+        out["ext_store_" + k + "_of_extend"] = c / sum(cyc)
 cc, cg = list(s["extend_class_cycles"]), list(s["extend_class_groups"])
 if sum(cc):  # k_extend wave time by the class of the group: camera, A, B, C (trace / shade share, cycles per group)
     for i, k in enumerate(("cam", "A", "B", "C")):
