@@ -33,6 +33,7 @@
 #include "../host/render_plan.h"
 #include "../host/aov_plan.h"
 #include "../host/film_tools.h"
+#include "../host/glare_model.h"
 
 #include <hip/hip_runtime.h>
 
@@ -3056,6 +3057,22 @@ int post_soft_blocks(int w, int h);
 // queue the imageinfo passes on dev->stream; hist (4 * bins ints, zeroed on the stream before) may be nullptr
 void launch_imageinfo(igx_device* dev, const float* film, int w, int h, float scale, bool stats, int bins, float* plane, const PostSlab& s,
                       PostResult* res, int* hist);
+// Daylight glare (k_glare_scan): the camera on the film, the scale and the two
+// luminance levels of glare_model.h; the slab holds the six per-block sums,
+// one entry per POST_CHUNK pixels (6 * post_lum_blocks(n) words at `base`)
+struct GlareArgs {
+    CameraModel cam;
+    int w, h;
+    float scale, lum_source, lum_max;
+};
+struct GlareSlab {
+    float *ev, *omega, *lum, *x, *y;
+    int* n;
+};
+// queue k_glare_scan on dev->stream; overlay (device memory, a.w * a.h words) may be nullptr
+void launch_glare(igx_device* dev, const float* film, const GlareArgs& a, float* slab, uint32_t* overlay);
+// the slab copied to the host -> the output (block order, glare_finish)
+igx_glare_output glare_finish_slab(float* slab_host, size_t blocks, const igx_glare_settings& set, const CameraModel& cam, int w, int h);
 #if IGX_PART == 6
 #include "igx_post.h"
 #endif
@@ -4637,6 +4654,75 @@ extern "C" igx_status igx_imageinfo_film(igx_device* dev, const float* film_dev,
     igx_status st = drain(dev);
     if (st != IGX_OK) return st;
     return imageinfo_run(dev, film_dev, width, height, is->scale, is, out);
+}
+
+// Device::evaluateGlare (Device.cpp:1689-1723).  The queue is drained; film:
+// w * h RGB floats in device memory.  One k_glare_scan, then the slab (and a
+// host overlay's image) comes back and the tail runs on the host.  A host
+// overlay keeps the words of the pixels at or below the threshold: the kernel
+// writes into a zeroed device image, whose non-zero words (alpha is 255) are
+// merged into the caller's buffer.
+static igx_status glare_run(igx_device* dev, const float* film, int w, int h, float scale, const igx_glare_settings* gs, uint32_t* overlay,
+                            bool overlay_on_device, igx_glare_output* out) {
+    const igx_camera& c = dev->cam_desc;
+    if (c.dir[0] == 0 && c.dir[1] == 0 && c.dir[2] == 0)
+        return fail(dev, IGX_ERR_NO_SCENE, "evaluate_glare needs a camera: upload a scene or call igx_set_camera");
+    const size_t n = (size_t)w * h, blocks = (size_t)post_lum_blocks(n);
+    igx_glare_settings set = *gs;
+    set.scale = scale;
+    GlareArgs a{};
+    a.cam = make_camera(dev, w, h);
+    a.w = w;
+    a.h = h;
+    a.scale = scale;
+    a.lum_source = igx::glare_lum_source(set);
+    a.lum_max = igx::glare_lum_max(set);
+    igx_status st = post_reserve(dev, POST_SLAB, igx::GLARE_SUMS * blocks * sizeof(float));
+    if (st != IGX_OK) return st;
+    uint32_t* dst = overlay;
+    if (overlay && !overlay_on_device) {
+        if ((st = post_reserve(dev, POST_PIXELS, n * sizeof(uint32_t))) != IGX_OK) return st;
+        dst = (uint32_t*)dev->post_buf[POST_PIXELS];
+        HIPCHK(hipMemsetAsync(dst, 0, n * sizeof(uint32_t), dev->stream));
+    }
+    float* slab = (float*)dev->post_buf[POST_SLAB];
+    launch_glare(dev, film, a, slab, dst);
+    HIPCHK(hipGetLastError());
+    std::vector<float> back(igx::GLARE_SUMS * blocks);
+    std::vector<uint32_t> image(overlay && !overlay_on_device ? n : 0);
+    HIPCHK(hipMemcpyAsync(back.data(), slab, back.size() * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
+    if (!image.empty()) HIPCHK(hipMemcpyAsync(image.data(), dst, n * sizeof(uint32_t), hipMemcpyDeviceToHost, dev->stream));
+    HIPCHK(hipStreamSynchronize(dev->stream));
+    *out = glare_finish_slab(back.data(), blocks, set, a.cam, w, h);
+    for (size_t i = 0; i < image.size(); ++i)
+        if (image[i]) overlay[i] = image[i];
+    return IGX_OK;
+}
+
+extern "C" igx_status igx_evaluate_glare(igx_device* dev, const char* aov, const igx_glare_settings* gs, uint32_t* overlay_host,
+                                         size_t pixel_count, igx_glare_output* out) {
+    if (!dev || !gs || !out) return IGX_ERR_INVALID_ARGUMENT;
+    const float* film = nullptr;
+    float scale = 0;
+    igx_status st = post_named_film(dev, aov, gs->scale, &film, &scale);
+    if (st != IGX_OK) return st;
+    if (!film) {
+        *out = igx_glare_output{0, 0, 0, 0, 0};
+        return IGX_OK;
+    }
+    if (pixel_count * 3 != dev->fb_count)
+        return fail(dev, IGX_ERR_INVALID_ARGUMENT, "evaluate_glare size mismatch: expected " + std::to_string(dev->fb_count / 3) + " pixels");
+    return glare_run(dev, film, dev->fb_w, dev->fb_h, scale, gs, overlay_host, false, out);
+}
+
+extern "C" igx_status igx_evaluate_glare_film(igx_device* dev, const float* film_dev, int32_t width, int32_t height,
+                                              const igx_glare_settings* gs, uint32_t* overlay, int32_t overlay_on_device,
+                                              igx_glare_output* out) {
+    if (!dev || !film_dev || !gs || !out || width <= 0 || height <= 0) return IGX_ERR_INVALID_ARGUMENT;
+    HIPCHK(hipSetDevice(dev->hip_device));
+    igx_status st = drain(dev);
+    if (st != IGX_OK) return st;
+    return glare_run(dev, film_dev, width, height, gs->scale, gs, overlay, overlay_on_device != 0, out);
 }
 
 extern "C" igx_status igx_pack_tiles(igx_device* dev, const igx_render_params* p, float* dst, size_t count) {

@@ -12,6 +12,10 @@
 //                k_info_soft  3x3 windows of the plane: soft min / max / median
 //                k_info_final one block reduces both slabs in a fixed order
 //                k_info_hist  four histograms (LDS, flushed with integer atomics)
+//   k_glare_scan entrypoints/glare.art in one pass: per pixel the luminance and
+//                the solid angle between its four corner directions
+//                (host/glare_model.h), per block the six sums of the daylight
+//                glare probability, and the overlay words of the glare source
 //
 // No float atomics: every float sum is a fixed tree (lane run -> wave shuffle
 // -> block -> slab -> k_info_final), so a result is the same bits every run.
@@ -290,7 +294,100 @@ __global__ void __launch_bounds__(POST_BLOCK) k_info_hist(const float* __restric
         if (lh[i]) atomicAdd(&hist[i], lh[i]);
 }
 
+// Daylight glare (entrypoints/glare.art; host/glare_model.h states the
+// arithmetic and the order of the sums): block b takes pixels [b * POST_CHUNK,
+// ...) as k_info_lum does.  A thread's 4 pixels are consecutive, so within a
+// film row the right-hand corner directions of one pixel are the left-hand
+// ones of the next and stay in registers (10 camera directions per 4 pixels
+// instead of 16; a direction is a pure function of its lattice point, so the
+// bits are those of evaluating every corner).  Each pixel's luminance and solid
+// angle are evaluated once and feed the six sums, which go to slab entry b;
+// with `overlay` the pixels above the threshold store their heat-map word.
+// vec: the film is 16-byte aligned.
+static_assert(igx::GLARE_BLOCK == POST_BLOCK && igx::GLARE_ITERS == POST_ITERS && igx::GLARE_CHUNK == POST_CHUNK,
+              "glare_host repeats this kernel's reduction order");
+__global__ void __launch_bounds__(POST_BLOCK) k_glare_scan(const float* __restrict__ film, size_t n, GlareArgs a, GlareSlab s,
+                                                           uint32_t* __restrict__ overlay, int vec) {
+    __shared__ float lf[POST_BLOCK / 64];
+    __shared__ int li[POST_BLOCK / 64];
+    const size_t base = (size_t)blockIdx.x * POST_CHUNK;
+    const int w = a.w, h = a.h;
+    igx::GlareSums acc{0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < POST_ITERS; ++k) {
+        const size_t p = base + ((size_t)k * POST_BLOCK + threadIdx.x) * 4;
+        if (p >= n) break;
+        const int cnt = n - p < 4 ? (int)(n - p) : 4;
+        float c[12];
+        if (vec && cnt == 4) {
+            const float4* f4 = reinterpret_cast<const float4*>(film + 3 * p);
+            const float4 v0 = f4[0], v1 = f4[1], v2 = f4[2];
+            c[0] = v0.x, c[1] = v0.y, c[2] = v0.z, c[3] = v0.w, c[4] = v1.x, c[5] = v1.y;
+            c[6] = v1.z, c[7] = v1.w, c[8] = v2.x, c[9] = v2.y, c[10] = v2.z, c[11] = v2.w;
+        } else {
+            for (int j = 0; j < 12; ++j) c[j] = j < 3 * cnt ? film[3 * p + j] : 0.0f;
+        }
+        int y = (int)(p / (size_t)w);
+        int x = (int)(p - (size_t)y * w);
+        igx::CamVec r1{}, r2{}, r3{}, r4{};
+        bool carry = false; // r4 / r3 of the previous pixel are this one's r1 / r2
+        for (int j = 0; j < cnt; ++j) {
+            if (carry) {
+                r1 = r4;
+                r2 = r3;
+            } else {
+                r1 = igx::glare_pixel_dir(a.cam, w, h, x, y);
+                r2 = igx::glare_pixel_dir(a.cam, w, h, x, y + 1);
+            }
+            r3 = igx::glare_pixel_dir(a.cam, w, h, x + 1, y + 1);
+            r4 = igx::glare_pixel_dir(a.cam, w, h, x + 1, y);
+            const float lum = igx::glare_luminance(c[3 * j], c[3 * j + 1], c[3 * j + 2], a.scale);
+            if (igx::glare_add_pixel(acc, a.cam, x, y, lum, a.lum_source, r1, r2, r3, r4) && overlay)
+                overlay[p + j] = igx::glare_overlay(lum, a.lum_source, a.lum_max);
+            carry = ++x < w;
+            if (x == w) {
+                x = 0;
+                ++y;
+            }
+        }
+    }
+    const float ev = post_block_reduce(acc.ev, PostAdd{}, lf);
+    const int cnt = post_block_reduce(acc.n, PostAdd{}, li);
+    const float om = post_block_reduce(acc.omega, PostAdd{}, lf);
+    const float lm = post_block_reduce(acc.lum, PostAdd{}, lf);
+    const float sx = post_block_reduce(acc.x, PostAdd{}, lf);
+    const float sy = post_block_reduce(acc.y, PostAdd{}, lf);
+    if (threadIdx.x == 0) {
+        s.ev[blockIdx.x] = ev;
+        s.n[blockIdx.x] = cnt;
+        s.omega[blockIdx.x] = om;
+        s.lum[blockIdx.x] = lm;
+        s.x[blockIdx.x] = sx;
+        s.y[blockIdx.x] = sy;
+    }
+}
+
 static bool post_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+GlareSlab glare_slab(float* base, size_t blocks) {
+    return GlareSlab{base, base + blocks, base + 2 * blocks, base + 3 * blocks, base + 4 * blocks, (int*)(base + 5 * blocks)};
+}
+
+void launch_glare(igx_device* dev, const float* film, const GlareArgs& a, float* slab, uint32_t* overlay) {
+    const size_t n = (size_t)a.w * a.h;
+    const int blocks = post_lum_blocks(n);
+    hipLaunchKernelGGL(k_glare_scan, dim3(blocks), dim3(POST_BLOCK), 0, dev->stream, film, n, a, glare_slab(slab, blocks), overlay,
+                       post_aligned16(film) ? 1 : 0);
+}
+
+// the tail of the evaluation, on the host in this part's arithmetic (no
+// -fapprox-func): the slab's entries added in block order, then glare_finish
+igx_glare_output glare_finish_slab(float* slab_host, size_t blocks, const igx_glare_settings& set, const CameraModel& cam, int w, int h) {
+    const GlareSlab s = glare_slab(slab_host, blocks);
+    igx::GlareSums total{0, 0, 0, 0, 0, 0};
+    for (size_t b = 0; b < blocks; ++b)
+        total = igx::glare_sums_add(total, igx::GlareSums{s.ev[b], s.n[b], s.omega[b], s.lum[b], s.x[b], s.y[b]});
+    return igx::glare_finish(total, set, cam, w, h);
+}
 
 void launch_tonemap(igx_device* dev, const float* film, size_t pixels, const PostTonemap& a, uint32_t* out) {
     const size_t work = (pixels + 3) / 4;

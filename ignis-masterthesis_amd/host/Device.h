@@ -27,13 +27,17 @@
 //     file;
 //   * the framebuffer, statistics, resize and release calls map one to one.
 // tonemap / evaluateGlare / imageinfo / bake (Device.h:66-69) are outside the
-// traced path: tonemap and imageinfo run on the device over the film where it
-// lies (igx_tonemap / igx_imageinfo: entrypoints/tonemap.art and
-// entrypoints/imageinfo.art with core/color.art as HIP kernels; only the packed
-// image or the statistics are copied back; film_tools.h keeps the same
-// arithmetic as host loops); evaluateGlare and bake have
-// no igx counterpart (the glare shader needs the camera's solid-angle model,
-// bake a compiled shading-tree shader) and log and return an empty result.
+// traced path: tonemap, imageinfo and evaluateGlare run on the device over the
+// film where it lies (igx_tonemap / igx_imageinfo / igx_evaluate_glare:
+// entrypoints/tonemap.art, imageinfo.art and glare.art with core/color.art as
+// HIP kernels; only the packed image, the statistics or the glare figures and
+// the overlay are copied back; film_tools.h and glare_model.h keep the same
+// arithmetic as host loops).  The reference compiles its glare shader only
+// with options().Glare.Enabled (Runtime.cpp:567-568, TechniqueVariant.h:23);
+// here that is TechniqueVariantShaderSet::GlareEnabled, and evaluateGlare
+// after a render without it logs and returns an empty result.  bake has no
+// igx counterpart (it needs a compiled shading-tree shader): logged, nothing
+// written.
 // Errors from the C-ABI become std::runtime_error, which a Runtime turns into
 // its bool / IG_LOG path (Runtime.cpp:159-162); an unknown AOV name alone gives
 // the reference's empty accessor {nullptr, 0}.
@@ -77,6 +81,9 @@ static_assert(sizeof(Ray) == 8 * sizeof(float), "ray-list layout of igx_render_p
 
 struct TechniqueVariantShaderSet {
     igx_shading_view shading{};
+    // the variant carries a glare shader (TechniqueVariant.h:23, compiled with
+    // options().Glare.Enabled only): evaluateGlare works after a render with it
+    bool GlareEnabled = false;
 };
 struct TechniqueVariantInfo {};
 using Vector3f = std::array<float, 3>;
@@ -303,6 +310,7 @@ public:
             p.tile_stride = s.tile_stride;
         }
         check(igx_render(mDev, &p));
+        mGlareEnabled = shader_set.GlareEnabled;
         mWidth = s.width;
         mHeight = s.rays ? 1 : s.height;
     }
@@ -393,11 +401,24 @@ public:
         const igx_tonemap_settings s{(int32_t)ts.Method, ts.UseGamma ? 1 : 0, ts.Scale, ts.ExposureFactor, ts.ExposureOffset};
         check(igx_tonemap(mDev, name.c_str(), &s, out_pixels, mWidth * mHeight));
     }
-    // The glare shader (Device.cpp:1689-1723) evaluates the daylight glare
-    // probability over the camera's solid-angle model; igx has none: logged, empty
-    GlareOutput evaluateGlare(uint32_t*, const GlareSettings&) {
-        std::fprintf(stderr, "igx: evaluateGlare is not provided by the igx device (outside the traced path)\n");
-        return GlareOutput{0, 0, 0, 0, 0};
+    // entrypoints/glare.art on the device over the AOV's film through the
+    // current camera (igx_evaluate_glare, Device.cpp:1689-1723).  out_pixels
+    // (may be null): the pixels of the glare source get their heat-map word,
+    // the rest stay as they are.  Without a glare shader in the last rendered
+    // shader set (GlareEnabled), as in the reference without
+    // options().Glare.Enabled, or with an unknown AOV: logged, the empty
+    // result, out_pixels untouched.
+    GlareOutput evaluateGlare(uint32_t* out_pixels, const GlareSettings& gs) {
+        const std::string name = gs.AOV ? gs.AOV : "";
+        if (!mGlareEnabled || !knownAOV(name) || mWidth * mHeight == 0) {
+            std::fprintf(stderr, "igx: evaluateGlare: %s\n",
+                         !mGlareEnabled ? "the last rendered shader set has no glare shader (GlareEnabled)" : "no such film");
+            return GlareOutput{0, 0, 0, 0, 0};
+        }
+        const igx_glare_settings s{gs.Scale, gs.LuminanceMax, gs.LuminanceAverage, gs.LuminanceMultiplier, gs.VerticalIlluminance};
+        igx_glare_output o{};
+        check(igx_evaluate_glare(mDev, name.c_str(), &s, out_pixels, mWidth * mHeight, &o));
+        return GlareOutput{o.dgp, o.vertical_illuminance, o.num_pixels, o.avg_lum, o.avg_omega};
     }
     // entrypoints/imageinfo.art on the device over the AOV's film
     // (igx_imageinfo); an unknown AOV or no film yet gives the all-zero result
@@ -492,6 +513,7 @@ private:
     ShadingCopy mLast;
     igx_camera mCamera{};
     DenoiserSettings mDenoiser;
+    bool mGlareEnabled = false; // of the last rendered shader set
     size_t mWidth = 0, mHeight = 0;
     std::unordered_map<std::string, std::vector<float>> mHostFB; // per AOV name
     Statistics mStats;

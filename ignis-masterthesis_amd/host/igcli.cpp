@@ -21,8 +21,14 @@
 // `imageinfo {json}` with the film's luminance statistics (and with BINS the
 // four histograms), --ppm FILE [--tonemap N] [--gamma] writes the tonemapped
 // film as a binary PPM; both run on the device (Device::imageinfo /
-// Device::tonemap).  Options of the reference's other targets and of its
-// shader compiler are refused with a message.
+// Device::tonemap).  --glare [--glare-mul M] [--glare-ev E] prints one line
+// `glare: dgp D ev E avg_lum L omega O pixels N`: the daylight glare probability
+// of the film through the scene's camera (Device::evaluateGlare), with the
+// threshold M (default 5) times imageinfo's average, the colour ramp up to its
+// soft maximum, as the viewer calls it (UI.cpp:651), and the vertical
+// illuminance computed unless E is given; with --ppm the heat map of the glare
+// source lies over the tonemapped image.  Options of the reference's other
+// targets and of its shader compiler are refused with a message.
 #include "Device.h"
 #include "igx_scene.h"
 
@@ -40,6 +46,7 @@ static void usage() {
                  "             [--width W --height H] [--eye X Y Z] [--dir X Y Z] [--up X Y Z] [--stats]\n"
                  "             [--denoise-aovs [--denoiser-aov-every-iteration] [--denoiser-follow-specular]]\n"
                  "             [--imageinfo [BINS]] [--ppm out.ppm [--tonemap 0..4] [--gamma]]\n"
+                 "             [--glare [--glare-mul M] [--glare-ev E]]\n"
                  "             [-o out.exr|out.pfm]\n");
 }
 
@@ -52,6 +59,8 @@ int main(int argc, char** argv) {
     std::string ppm_path;
     int tonemap_method = 0;
     bool tonemap_gamma = false;
+    bool glare = false;
+    float glare_mul = 5.0f, glare_ev = -1.0f; // --glare-ev: < 0 = computed
     IG::Device::DenoiserSettings denoiser;
     IG::ParameterSet params; // the camera orientation overrides (__camera_eye / _dir / _up)
     for (int i = 1; i < argc; ++i) {
@@ -94,6 +103,9 @@ int main(int argc, char** argv) {
         else if (a == "--ppm") ppm_path = next();
         else if (a == "--tonemap") tonemap_method = std::atoi(next());
         else if (a == "--gamma") tonemap_gamma = true;
+        else if (a == "--glare") glare = true;
+        else if (a == "--glare-mul") glare_mul = (float)std::atof(next());
+        else if (a == "--glare-ev") glare_ev = (float)std::atof(next());
         else if (a == "-o" || a == "--output") out_path = next();
         else if (a == "--gpu" || a == "--no-progress" || a == "--no-color" || a == "-q" || a == "--quiet") {}
         else if (a == "--cpu" || a == "--cpu-arch" || a == "--cpu-threads" || a == "--cpu-vectorwidth") {
@@ -126,6 +138,7 @@ int main(int argc, char** argv) {
         IG::SceneDatabase db;
         IG::TechniqueVariantShaderSet shaders;
         IG::serialize_scene(*desc, db, shaders.shading);
+        shaders.GlareEnabled = glare;
         IG::Device::SetupSettings ss;
         ss.target = IG::Target::makeGPU(device);
         ss.AcquireStats = stats;
@@ -181,9 +194,19 @@ int main(int argc, char** argv) {
             }
             std::printf("}\n");
         }
+        std::vector<uint32_t> px;
         if (!ppm_path.empty()) {
-            std::vector<uint32_t> px((size_t)W * H, 0xff000000u);
+            px.assign((size_t)W * H, 0xff000000u);
             dev.tonemap(px.data(), IG::TonemapSettings{"", (size_t)tonemap_method, tonemap_gamma, 1.0f, 1.0f, 0.0f});
+        }
+        if (glare) {
+            const IG::ImageInfoOutput io = dev.imageinfo(IG::ImageInfoSettings{"", 1.0f, 0, nullptr, nullptr, nullptr, nullptr, false, false});
+            const IG::GlareOutput g = dev.evaluateGlare(px.empty() ? nullptr : px.data(),
+                                                        IG::GlareSettings{"", 1.0f, io.SoftMax, io.Average, glare_mul, glare_ev});
+            std::printf("glare: dgp %.9g ev %.9g avg_lum %.9g omega %.9g pixels %d\n", g.DGP, g.VerticalIlluminance, g.AvgLum, g.AvgOmega,
+                        g.NumPixels);
+        }
+        if (!ppm_path.empty()) {
             FILE* f = std::fopen(ppm_path.c_str(), "wb");
             if (!f) { std::fprintf(stderr, "cannot write %s\n", ppm_path.c_str()); return 1; }
             std::fprintf(f, "P6\n%d %d\n255\n", W, H);

@@ -21,8 +21,8 @@ import os
 import numpy as np
 
 from . import _native
-from ._native import (EXPORTED_SYMBOLS, LIB_PATH, ImageInfoOutput, ImageInfoSettings, RenderParams, Stats,
-                      TonemapSettings, lib)
+from ._native import (EXPORTED_SYMBOLS, LIB_PATH, GlareOutput, GlareSettings, ImageInfoOutput, ImageInfoSettings,
+                      RenderParams, Stats, TonemapSettings, lib)
 
 __all__ = ["RuntimeOptions", "DenoiserSettings", "Scene", "Runtime", "loadFromFile", "loadFromString", "version",
            "EXPORTED_SYMBOLS", "LIB_PATH", "IgxError"]
@@ -412,6 +412,50 @@ class Device:
         return self._imageinfo(lambda st, out: self._lib.igx_imageinfo_film(self._h, C.c_void_p(ptr), int(w), int(h), st, out),
                                scale, bins, error_stats)
 
+    # ---- daylight glare probability on the device (igx_evaluate_glare) ----
+    def _evaluate_glare(self, call, shape, lum_max, lum_avg, lum_mul, vertical_illuminance, scale, overlay):
+        gs = GlareSettings(float(scale), float(lum_max), float(lum_avg), float(lum_mul), float(vertical_illuminance))
+        out = GlareOutput()
+        if overlay is not None:
+            overlay = np.ascontiguousarray(overlay, dtype=np.uint32).copy()
+            if overlay.shape != shape:
+                raise ValueError(f"overlay must have shape {shape}, not {overlay.shape}")
+        self._check(call(C.byref(gs), C.c_void_p(overlay.ctypes.data) if overlay is not None else None, C.byref(out)))
+        res = {k: getattr(out, k) for k, _ in GlareOutput._fields_}
+        return res if overlay is None else (res, overlay)
+
+    def evaluate_glare(self, name=None, lum_max=0.0, lum_avg=0.0, lum_mul=5.0, vertical_illuminance=-1.0, scale=1.0,
+                       overlay=None):
+        """Device::evaluateGlare of the film or a named AOV (scaled by scale /
+        its iteration count) through the current camera: a dict of dgp,
+        vertical_illuminance, avg_lum, avg_omega (the source's summed solid
+        angle) and num_pixels.  lum_max and lum_avg are imageinfo's soft_max
+        and avg; a vertical_illuminance >= 0 is used as given.  With `overlay`
+        (an (h, w) uint32 image, e.g. tonemap()'s) also a copy of it with the
+        heat-map words of the pixels above the threshold laid over.  None
+        before the first render."""
+        if self._film is None:
+            return None
+        w, h = self._film
+        aov = name.encode() if name else None
+        return self._evaluate_glare(lambda gs, ov, out: self._lib.igx_evaluate_glare(self._h, aov, gs, ov, w * h, out), (h, w),
+                                    lum_max, lum_avg, lum_mul, vertical_illuminance, scale, overlay)
+
+    def evaluate_glare_film(self, ptr, w, h, lum_max=0.0, lum_avg=0.0, lum_mul=5.0, vertical_illuminance=-1.0, scale=1.0,
+                            overlay=None, overlay_ptr=None):
+        """igx_evaluate_glare_film over w * h * 3 floats at the device pointer
+        `ptr`, `scale` as given, the current camera on w x h.  `overlay` as for
+        evaluate_glare; with `overlay_ptr` (device memory for w * h words) the
+        words of the pixels above the threshold are stored there instead."""
+        if overlay_ptr is not None:
+            return self._evaluate_glare(
+                lambda gs, ov, out: self._lib.igx_evaluate_glare_film(self._h, C.c_void_p(ptr), int(w), int(h), gs,
+                                                                      C.c_void_p(overlay_ptr), 1, out),
+                (h, w), lum_max, lum_avg, lum_mul, vertical_illuminance, scale, None)
+        return self._evaluate_glare(
+            lambda gs, ov, out: self._lib.igx_evaluate_glare_film(self._h, C.c_void_p(ptr), int(w), int(h), gs, ov, 0, out),
+            (h, w), lum_max, lum_avg, lum_mul, vertical_illuminance, scale, overlay)
+
     def synchronize(self):
         self._check(self._lib.igx_synchronize(self._h))
 
@@ -581,6 +625,10 @@ class Runtime:
     def imageinfo(self, name="", **settings):
         """Runtime::imageinfo (Runtime.cpp:663): Device.imageinfo of the runtime's film or AOV."""
         return self.device.imageinfo(name or None, **settings)
+
+    def evaluateGlare(self, name="", **settings):
+        """Runtime::evaluateGlare (Runtime.cpp:640): Device.evaluate_glare of the runtime's film or AOV."""
+        return self.device.evaluate_glare(name or None, **settings)
 
     def getStatistics(self):
         return self.device.stats()

@@ -198,6 +198,16 @@ class ImageInfoOutput(C.Structure):
                 ("neg_count", C.c_int32)]
 
 
+class GlareSettings(C.Structure):
+    _fields_ = [("scale", C.c_float), ("lum_max", C.c_float), ("lum_avg", C.c_float), ("lum_mul", C.c_float),
+                ("vertical_illuminance", C.c_float)]
+
+
+class GlareOutput(C.Structure):
+    _fields_ = [("dgp", C.c_float), ("vertical_illuminance", C.c_float), ("avg_lum", C.c_float), ("avg_omega", C.c_float),
+                ("num_pixels", C.c_int32)]
+
+
 # every symbol include/igx.h and include/igx_scene.h declare
 EXPORTED_SYMBOLS = [
     "igx_scene_load_file", "igx_scene_load_string", "igx_scene_get_desc", "igx_scene_free", "igx_write_exr",
@@ -209,6 +219,7 @@ EXPORTED_SYMBOLS = [
     "igx_objscene_set_property", "igx_scene_from_objects", "igx_set_camera", "igx_camera_rays",
     "igx_clear_aov", "igx_aov_iteration_count", "igx_write_exr_layers",
     "igx_tonemap", "igx_imageinfo", "igx_tonemap_film", "igx_imageinfo_film", "igx_get_store_split",
+    "igx_evaluate_glare", "igx_evaluate_glare_film",
 ]
 
 _lib = None
@@ -288,6 +299,11 @@ def lib():
     L.igx_imageinfo_film.argtypes = [vp, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ImageInfoSettings), C.POINTER(ImageInfoOutput)]
     for name in ["igx_tonemap", "igx_imageinfo", "igx_tonemap_film", "igx_imageinfo_film"]:
         getattr(L, name).restype = C.c_int
+    if hasattr(L, "igx_evaluate_glare"):  # as above: an older IGX_LIB_PATH build has none
+        L.igx_evaluate_glare.argtypes = [vp, C.c_char_p, C.POINTER(GlareSettings), C.c_void_p, C.c_size_t, C.POINTER(GlareOutput)]
+        L.igx_evaluate_glare_film.argtypes = [vp, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(GlareSettings), C.c_void_p, C.c_int32,
+                                              C.POINTER(GlareOutput)]
+        L.igx_evaluate_glare.restype = L.igx_evaluate_glare_film.restype = C.c_int
     for name in ["igx_create", "igx_destroy", "igx_set_option", "igx_upload_scene", "igx_render", "igx_render_iterations",
                  "igx_get_framebuffer", "igx_framebuffer_device_ptr", "igx_get_aov", "igx_aov_device_ptr",
                  "igx_pack_tiles", "igx_clear", "igx_clear_aov", "igx_aov_iteration_count",
