@@ -2044,7 +2044,16 @@ __device__ __forceinline__ float principled_spec_trans_pdf(const Principled& p, 
     f3 pwo = make_positive_hemi(wo), pwi = neg(make_positive_hemi(wi));
     f3 H = normalize(add(pwi, mulf(pwo, p.eta)));
     float chi = dot(pwi, H), cho = dot(pwo, H);
-    return fabsf(bound_spec_pdf(pdf_vndf_ggx(frame_identity(), pwo, H, p.ru, p.rv)) * refr_jacobian(p.eta, chi, cho));
+    // getRefractionMicro (principled.art:73-80): a thin surface refracts through a lobe of
+    // its own roughness; one at or below 1e-4 is the delta distribution, whose pdf is 0
+    float ru = p.ru, rv = p.rv;
+    if (p.thin) {
+        const float f = 0.65f * p.ior - 0.35f;
+        ru = clampf(f * ru, 0, 1);
+        rv = clampf(f * rv, 0, 1);
+        if (ru <= 1e-4f || rv <= 1e-4f) return 0.0f;
+    }
+    return fabsf(bound_spec_pdf(pdf_vndf_ggx(frame_identity(), pwo, H, ru, rv)) * refr_jacobian(p.eta, chi, cho));
 }
 __device__ __forceinline__ float principled_pdf_local(const Principled& p, f3 wo, f3 wi) {
     if (fabsf(wo.z) <= 1e-5f || fabsf(wi.z) <= 1e-5f) return 0;

@@ -168,6 +168,7 @@ typedef struct {
     int faces;               /* shape emitter: primitive_count */
     float sel_pos[3], sel_dir[3], sel_flux; /* Light::position / direction / computeFlux */
     int sel_has_dir;
+    int desc_light;          /* image environment map: its igx_light (texture, scale, transform) */
 } olight;
 
 struct oracle_scene {
@@ -653,11 +654,13 @@ oracle_scene* oracle_scene_create(const igx_scene_desc* desc) {
     for (int pass = 0; pass < 2; ++pass)
         for (uint32_t l = 0; l < desc->num_lights; ++l) {
             const igx_light* L = &desc->lights[l];
-            int inf = L->type == IGX_LIGHT_ENV || L->type == IGX_LIGHT_DIRECTIONAL || L->type == IGX_LIGHT_SUN;
+            int inf = L->type == IGX_LIGHT_ENV || L->type == IGX_LIGHT_DIRECTIONAL || L->type == IGX_LIGHT_SUN ||
+                      L->type == IGX_LIGHT_ENVMAP;
             if ((pass == 0) != inf) continue;
             olight* o = &s->lights[k];
             o->type = L->type;
             o->infinite = inf;
+            o->desc_light = (int)l;
             o->delta = L->type == IGX_LIGHT_POINT || L->type == IGX_LIGHT_SPOT || L->type == IGX_LIGHT_DIRECTIONAL ||
                        L->type == IGX_LIGHT_SUN;
             memcpy(o->rad, L->radiance, sizeof(o->rad));
@@ -1568,7 +1571,7 @@ static osample lobe_sample(const obsdf* b, int lobe, rng_t* r, v3 out) {
  * identity frame. -------------------------------------------------------- */
 typedef struct {
     v3 base;
-    float eta, ru, rv, dtr, str, stint, flat, metal, sheen, sheen_tint, cc, ccg, ccr;
+    float eta, ior, ru, rv, dtr, str, stint, flat, metal, sheen, sheen_tint, cc, ccg, ccr;
     int thin, cc_top, entering;
 } oprin;
 
@@ -1592,6 +1595,7 @@ static oprin oprin_make(const igx_material* m, const osurf* sf) {
     p.thin = m->thin != 0;
     p.cc_top = m->clearcoat_top_only != 0;
     p.entering = sf->entering;
+    p.ior = m->ior;
     p.eta = (sf->entering || p.thin) ? 1 / m->ior : m->ior;
     return p;
 }
@@ -1738,7 +1742,17 @@ static float prin_refl_pdf(const oprin* p, v3 wo, v3 wi) {
 static float prin_trans_pdf(const oprin* p, v3 wo, v3 wi) {
     v3 a = hemi_pos(wo), b = vneg(hemi_pos(wi));
     v3 H = vnormalize(vadd(b, vmulf(a, p->eta)));
-    return fabsf(prin_bound(vndf_pdf(&PRIN_IDENTITY, a, H, p->ru, p->rv)) * jac_refr(p->eta, vdot(b, H), vdot(a, H)));
+    /* getRefractionMicro (bsdf/principled.art:73-80): a thin surface refracts
+     * through a lobe of its own roughness; one at or below 1e-4 is the delta
+     * distribution (core/microfacet.art:298), whose pdf is 0 */
+    float ru = p->ru, rv = p->rv;
+    if (p->thin) {
+        const float f = 0.65f * p->ior - 0.35f;
+        ru = clampf_(f * ru, 0, 1);
+        rv = clampf_(f * rv, 0, 1);
+        if (ru <= 1e-4f || rv <= 1e-4f) return 0.0f;
+    }
+    return fabsf(prin_bound(vndf_pdf(&PRIN_IDENTITY, a, H, ru, rv)) * jac_refr(p->eta, vdot(b, H), vdot(a, H)));
 }
 static float prin_pdf_local(const oprin* p, v3 wo, v3 wi) {
     if (fabsf(wo.z) <= 1e-5f || fabsf(wi.z) <= 1e-5f) return 0;
@@ -1934,6 +1948,79 @@ static void path_begin(const oracle_scene* s, const oracle_params* p, int x, int
     q->y = y;
 }
 
+/* ---- image environment map, as seen by a ray that leaves the scene --------
+ * make_environment_light (light/env.art:161-164): scale * tex(map_env_uv(
+ * switch_env_up(transform * dir))) (env.art:13-21) through the image texture of
+ * texture/image.art (borders :9-39, texel points :53-77, filters :79-143).
+ * Only this emission is restated: sampling the map (its CDF) is not, so the
+ * oracle renders such a scene with "nee": false only. */
+static int tex_border(int wrap, int x, int w) {
+    if (wrap == IGX_WRAP_CLAMP) return x < 0 ? 0 : (x > w - 1 ? w - 1 : x);
+    if (wrap == IGX_WRAP_MIRROR) {
+        int t = x < 0 ? -1 - x : x, i = t / w, k = t - i * w;
+        return (i & 1) == 0 ? w - 1 - k : k;
+    }
+    int t = x % w;
+    return t < 0 ? t + w : t;
+}
+static v3 tex_fetch(const igx_image* im, int x, int y) {
+    const size_t at = (size_t)y * (size_t)im->width + (size_t)x;
+    if (im->format == IGX_IMAGE_FLOAT4) {
+        const float* p = (const float*)im->pixels + 4 * at;
+        return V(p[0], p[1], p[2]);
+    }
+    if (im->format == IGX_IMAGE_MONO8) {
+        const float g = ((const uint8_t*)im->pixels)[at] / 255.0f;
+        return V(g, g, g);
+    }
+    const uint8_t* p = (const uint8_t*)im->pixels + 4 * at;
+    return V(p[0] / 255.0f, p[1] / 255.0f, p[2] / 255.0f);
+}
+static float cubic_w0(float a) { return (a * (a * (-a + 3) - 3) + 1) / 6; }
+static float cubic_w1(float a) { return (a * a * (3 * a - 6) + 4) / 6; }
+static float cubic_w2(float a) { return (a * (a * (-3 * a + 3) + 3) + 1) / 6; }
+static float cubic_w3(float a) { return (a * a * a) / 6; }
+static v3 tex_lookup(const igx_scene_desc* d, const igx_texture* tx, float u0, float v0) {
+    const igx_image* im = &d->images[tx->image];
+    const float* m = tx->transform;
+    const float u = m[0] * u0 + m[1] * v0 + m[2], v = m[3] * u0 + m[4] * v0 + m[5];
+    const int w = im->width, h = im->height;
+    const float half = tx->filter == IGX_FILTER_NEAREST ? 0.0f : 0.5f;
+    const float pu = u * (float)w - half, pv = v * (float)h - half;
+    const float fu = floorf(pu), fv = floorf(pv);
+    const int ix = (int)fu, iy = (int)fv;
+    const float fx = pu - fu, fy = pv - fv;
+    if (tx->filter == IGX_FILTER_NEAREST) return tex_fetch(im, tex_border(tx->wrap_u, ix, w), tex_border(tx->wrap_v, iy, h));
+    if (tx->filter == IGX_FILTER_BILINEAR) {
+        const int x0 = tex_border(tx->wrap_u, ix, w), x1 = tex_border(tx->wrap_u, ix + 1, w);
+        const int y0 = tex_border(tx->wrap_v, iy, h), y1 = tex_border(tx->wrap_v, iy + 1, h);
+        return clerp(clerp(tex_fetch(im, x0, y0), tex_fetch(im, x1, y0), fx),
+                     clerp(tex_fetch(im, x0, y1), tex_fetch(im, x1, y1), fx), fy);
+    }
+    const float g0x = cubic_w0(fx) + cubic_w1(fx), g1x = cubic_w2(fx) + cubic_w3(fx);
+    const float g0y = cubic_w0(fy) + cubic_w1(fy), g1y = cubic_w2(fy) + cubic_w3(fy);
+    const int x0 = tex_border(tx->wrap_u, (int)floorf((float)ix + (cubic_w1(fx) / g0x - 1) + 0.5f), w);
+    const int y0 = tex_border(tx->wrap_v, (int)floorf((float)iy + (cubic_w1(fy) / g0y - 1) + 0.5f), h);
+    const int x1 = tex_border(tx->wrap_u, (int)floorf((float)ix + (cubic_w3(fx) / g1x + 1) + 0.5f), w);
+    const int y1 = tex_border(tx->wrap_v, (int)floorf((float)iy + (cubic_w3(fy) / g1y + 1) + 0.5f), h);
+    return vadd(vadd(vmulf(tex_fetch(im, x0, y0), g0x * g0y), vmulf(tex_fetch(im, x1, y0), g1x * g0y)),
+                vadd(vmulf(tex_fetch(im, x0, y1), g0x * g1y), vmulf(tex_fetch(im, x1, y1), g1x * g1y)));
+}
+static v3 envmap_emission(const oracle_scene* s, const olight* L, v3 dir) {
+    const igx_light* dl = &s->desc.lights[L->desc_light];
+    const float* t = dl->sky_transform;
+    const v3 l = V(t[0] * dir.x + t[1] * dir.y + t[2] * dir.z, t[3] * dir.x + t[4] * dir.y + t[5] * dir.z,
+                   t[6] * dir.x + t[7] * dir.y + t[8] * dir.z);
+    const v3 e = V(l.x, l.z, l.y); /* switch_env_up */
+    const float theta = acosf(e.z);
+    float phi = atan2f(e.y, e.x);
+    if (phi < 0) phi += 2 * PI_;
+    float u = phi / (2 * PI_) + 0.25f;
+    u -= floorf(u);
+    const v3 c = tex_lookup(&s->desc, &s->desc.textures[dl->env_texture], u, 1 - theta / PI_);
+    return V(c.x * dl->env_scale[0], c.y * dl->env_scale[1], c.z * dl->env_scale[2]);
+}
+
 /* One vertex of technique/pathtracer.art:52-200 for the closest hit `h` of the
  * path's ray (h->ent < 0: a miss): the radiance gathered there (*Lacc: on_hit
  * emission with MIS, or on_miss), the NEE shadow ray and its colour
@@ -1951,6 +2038,7 @@ static int path_shade(const oracle_scene* s, opath* q, const ohit* h, v3* Lacc, 
             const olight* L = &s->lights[li];
             if (L->delta) continue;
             v3 emit = V(L->rad[0], L->rad[1], L->rad[2]);
+            if (L->type == IGX_LIGHT_ENVMAP) emit = envmap_emission(s, L, ray->dir);
             float pdf_s = 1 / (4 * PI_);
             float sel = s->selector == IGX_SELECT_UNIFORM ? uni_pdf : select_pdf(s, li, ray->org);
             float mis = tech->nee ? 1 / (1 + q->inv_pdf * sel * pdf_s) : 1.0f;

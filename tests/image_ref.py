@@ -1,7 +1,9 @@
 """numpy restatements for the image texture tests (no GPU, no project code):
-the packed-image byte mapping and row flip of the reference's Image.cpp, and the
-image texture arithmetic of texture/image.art in float64."""
+the packed-image byte mapping and row flip of the reference's Image.cpp, the
+image texture arithmetic of texture/image.art and the environment map lookup of
+light/env.art in float64."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -135,3 +137,29 @@ def choice_is_stable(tex, filt, wrap_u, wrap_v, u, v, eps=1e-5):
             for a, b in zip(base, other):
                 ok &= a == b
     return ok
+
+
+LIGHT_ENVMAP = 10  # igx_light.type of an image environment map (include/igx_scene.h)
+
+
+def env_uv(m, d):
+    """map_env_uv(switch_env_up(m d)) in float64 (light/env.art:13-21)."""
+    l = d @ np.asarray(m, np.float64).reshape(3, 3).T
+    x, y, z = l[:, 0], l[:, 2], l[:, 1]
+    theta = np.arccos(np.clip(z, -1, 1))
+    phi = np.arctan2(y, x)
+    phi = np.where(phi < 0, phi + 2 * math.pi, phi)
+    t = phi / (2 * math.pi) + 0.25
+    return t - np.floor(t), 1 - theta / math.pi
+
+
+def env_radiance(desc, d, scale=None):
+    """scale * tex(map_env_uv(...)) of the scene's environment map in float64, (n, 3);
+    `scale` None is the light's own env_scale."""
+    light = [desc.lights[i] for i in range(desc.num_lights) if desc.lights[i].type == LIGHT_ENVMAP][0]
+    tx = desc.textures[light.env_texture]
+    tex = texels_float64(desc_image(desc, tx.image))
+    u, v = env_uv(light.sky_transform[:], d)
+    tu, tv = transform_uv(tx.transform[:], u, v)
+    scale = light.env_scale[:] if scale is None else scale
+    return sample(tex, tx.filter, tx.wrap_u, tx.wrap_v, tu, tv)[..., :3] * np.asarray(scale, np.float64), (tex, tx, tu, tv)

@@ -11,6 +11,7 @@ import pytest
 import daylight_ref as R
 import ignis_amd
 import image_ref as IR
+from image_ref import env_radiance, env_uv
 from ignis_amd import _native as N
 
 pytestmark = pytest.mark.gpu
@@ -45,27 +46,6 @@ def rotation(t):
     ry = np.array([[math.cos(ay), 0, math.sin(ay)], [0, 1, 0], [-math.sin(ay), 0, math.cos(ay)]])
     rz = np.array([[math.cos(az), -math.sin(az), 0], [math.sin(az), math.cos(az), 0], [0, 0, 1]])
     return np.vectorize(R.printed)(np.linalg.inv((rx @ ry @ rz).T))
-
-
-def env_uv(m, d):
-    """map_env_uv(switch_env_up(m d)) in float64 (light/env.art:13-21)."""
-    l = d @ np.asarray(m, np.float64).reshape(3, 3).T
-    x, y, z = l[:, 0], l[:, 2], l[:, 1]
-    theta = np.arccos(np.clip(z, -1, 1))
-    phi = np.arctan2(y, x)
-    phi = np.where(phi < 0, phi + 2 * math.pi, phi)
-    t = phi / (2 * math.pi) + 0.25
-    return t - np.floor(t), 1 - theta / math.pi
-
-
-def env_radiance(desc, d, scale=SCALE):
-    """scale * tex(map_env_uv(...)) of the scene's environment map in float64, (n, 3)."""
-    light = [desc.lights[i] for i in range(desc.num_lights) if desc.lights[i].type == N.LIGHT_ENVMAP][0]
-    tx = desc.textures[light.env_texture]
-    tex = IR.texels_float64(IR.desc_image(desc, tx.image))
-    u, v = env_uv(light.sky_transform[:], d)
-    tu, tv = IR.transform_uv(tx.transform[:], u, v)
-    return IR.sample(tex, tx.filter, tx.wrap_u, tx.wrap_v, tu, tv)[..., :3] * np.asarray(scale, np.float64), (tex, tx, tu, tv)
 
 
 @pytest.fixture(scope="module")
