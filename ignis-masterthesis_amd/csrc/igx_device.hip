@@ -609,6 +609,11 @@ __device__ __forceinline__ void class_pass(const SceneView& sv, f3 o, bool test_
     p_hit = s_hit = false;
     if (sv.num_enc <= 0 || !__ballot(test_p || test_s)) return;
     const f3 ip = fast_rcp3(pd), is = fast_rcp3(sd);
+    // one box per trip: the loop vectoriser otherwise takes two boxes at once
+    // with packed f32 operations (v_pk_add_f32 / v_pk_mul_f32, 18 of them and
+    // the moves that build their register pairs), which cost a wave what the
+    // two unpacked operations do (tools/vpk_probe.hip)
+#pragma clang loop vectorize(disable)
     for (int k = 0; k < sv.num_enc; ++k) {
         const float4 lo = sv.enc_box[2 * k], hi = sv.enc_box[2 * k + 1];
         const float lx = lo.x - o.x, hx = hi.x - o.x, ly = lo.y - o.y, hy = hi.y - o.y, lz = lo.z - o.z, hz = hi.z - o.z;

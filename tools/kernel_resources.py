@@ -1,25 +1,76 @@
 """Dev tool: per-kernel VGPR / SGPR / spill / scratch / LDS usage of the gfx950 code object in
-build/igx_device_p*.o (reads the AMDGPU metadata notes).
-usage: kernel_resources.py [name filter] [objects...]"""
+build/igx_device_p*.o (reads the AMDGPU metadata notes), and its static instruction mix from the
+disassembly of the same code object: all VALU (v_*), packed f32 VALU (v_pk_*_f32 and v_pk_mov_b32,
+what the SLP vectoriser makes of adjacent f32 operations), register moves (v_mov_b32 / _b64 and
+v_accvgpr moves), v_readlane / v_writelane (SGPR spills) and scratch instructions.
+usage: kernel_resources.py [--md] [name filter] [objects...]
+  --md   a markdown table (profiles/r11_kernel_resources.md) instead of one text line per kernel"""
 import glob
+import os
 import re
 import subprocess
 import sys
+import tempfile
 
 LLVM = "/opt/rocm/llvm/bin"
-pat = sys.argv[1] if len(sys.argv) > 1 else "k_"
-objs = sys.argv[2:] or sorted(glob.glob("ignis-masterthesis_amd/build/igx_device_p*.o"))
-notes = ""
-for obj in objs:
-    subprocess.run([f"{LLVM}/llvm-objcopy", "--dump-section=.hip_fatbin=/tmp/_fat.bin", obj, "/tmp/_host.o"], check=True)
-    subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", "--input=/tmp/_fat.bin",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=/tmp/_dev.co"], check=True)
-    notes += subprocess.run([f"{LLVM}/llvm-readelf", "--notes", "/tmp/_dev.co"], capture_output=True, text=True).stdout
-for b in notes.split(".name:")[1:]:
-    name = b.split("\n")[0].strip()
-    if pat not in name:
-        continue
-    dn = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-    g = lambda k: (re.search(r"\." + k + r":\s+(\d+)", b) or [None, "-"])[1]
-    print(f"{dn[:70]:70s} vgpr {g('vgpr_count'):>4} spill {g('vgpr_spill_count'):>3} sgpr {g('sgpr_count'):>4} sspill {g('sgpr_spill_count'):>3} "
-          f"priv {g('private_segment_fixed_size'):>4} lds {g('group_segment_fixed_size'):>6}")
+args = sys.argv[1:]
+md = "--md" in args
+args = [a for a in args if a != "--md"]
+pat = args[0] if args else "k_"
+objs = args[1:] or sorted(glob.glob("ignis-masterthesis_amd/build/igx_device_p*.o"))
+
+
+def instruction_mix(co):
+    """{mangled kernel name: counts} from llvm-objdump -d of one code object."""
+    dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True, check=True).stdout
+    mix, cur = {}, None
+    for line in dis.split("\n"):
+        m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
+        if m:
+            cur = mix.setdefault(m.group(1), dict(valu=0, pk=0, mov=0, lane=0, scratch=0))
+            continue
+        op = line.split()[0] if cur is not None and line.startswith(("\t", " ")) and line.split() else ""
+        if op.startswith("v_"):
+            cur["valu"] += 1
+            if re.match(r"v_pk_\w+_f32|v_pk_mov_b32", op):
+                cur["pk"] += 1
+            elif op.startswith(("v_mov_b", "v_accvgpr_")):
+                cur["mov"] += 1
+            elif op.startswith(("v_readlane", "v_writelane")):
+                cur["lane"] += 1
+        elif op.startswith("scratch_"):
+            cur["scratch"] += 1
+    return mix
+
+
+rows = []
+with tempfile.TemporaryDirectory() as tmp:
+    fat, host, co = (os.path.join(tmp, n) for n in ("fat.bin", "host.o", "dev.co"))
+    for obj in objs:
+        subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj, host], check=True)
+        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
+        notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
+        mix = None
+        for b in notes.split(".name:")[1:]:
+            name = b.split("\n")[0].strip()
+            if pat not in name:
+                continue
+            if mix is None:
+                mix = instruction_mix(co)
+            dn = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
+            g = lambda k: (re.search(r"\." + k + r":\s+(\d+)", b) or [None, "-"])[1]
+            rows.append((dn, [g(k) for k in ("vgpr_count", "vgpr_spill_count", "sgpr_count", "sgpr_spill_count",
+                                            "private_segment_fixed_size", "group_segment_fixed_size")],
+                         mix.get(name, dict(valu="-", pk="-", mov="-", lane="-", scratch="-"))))
+
+if md:
+    print("| kernel | vgpr | spill | sgpr | sspill | priv | lds | VALU | v_pk_*_f32 | v_mov | v_readlane/writelane | scratch |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for dn, r, m in rows:
+        short = re.sub(r"^void igxh::", "", dn).split("(")[0]
+        print(f"| `{short}` | " + " | ".join(r) + f" | {m['valu']} | {m['pk']} | {m['mov']} | {m['lane']} | {m['scratch']} |")
+else:
+    for dn, r, m in rows:
+        print(f"{dn[:70]:70s} vgpr {r[0]:>4} spill {r[1]:>3} sgpr {r[2]:>4} sspill {r[3]:>3} priv {r[4]:>4} lds {r[5]:>6} "
+              f"valu {m['valu']:>6} pk {m['pk']:>5} mov {m['mov']:>5} lane {m['lane']:>4} scratch {m['scratch']:>4}")
