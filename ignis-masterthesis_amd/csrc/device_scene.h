@@ -90,7 +90,8 @@ constexpr uint32_t INST_TRANSLATE = 1u << 29;
 // info (shape, material, vtx_offset, idx_offset) -> 7 x 16 B.
 constexpr int ENT_STRIDE = 7;
 
-enum : int32_t { MAT_DIFFUSE = 0, MAT_DIELECTRIC = 1, MAT_CONDUCTOR = 2, MAT_PLASTIC = 3, MAT_PRINCIPLED = 4 };
+enum : int32_t { MAT_DIFFUSE = 0, MAT_DIELECTRIC = 1, MAT_CONDUCTOR = 2, MAT_PLASTIC = 3, MAT_PRINCIPLED = 4,
+                 MAT_TENSORTREE = 5, MAT_KLEMS = 6 };
 // microfacet distribution of conductor / plastic specular lobes
 // (BSDF::setupRoughness, src/runtime/bsdf/BSDF.cpp:53-99)
 enum : int32_t { MF_DELTA = 0, MF_VNDF_GGX = 1, MF_GGX = 2, MF_BECKMANN = 3 };
@@ -106,6 +107,15 @@ struct DevMaterial {   // 128 B
                         // pad[1] = scale, pad[2..4] = the colour where the checker is 1 (kd elsewhere)
                         // image texture (IGX_TEXTURE_IMAGE, also on a principled base_color): pad[1..6] =
                         // the 2x3 uv transform, pad[7] = its TexRecord's place in the uv table (uint bits)
+    // Measured BSDFs (MAT_TENSORTREE, MAT_KLEMS; components k = 0..3: front reflection, front
+    // transmission, back reflection, back transmission, igx_measured):
+    //   dist = ndim (tensor tree); mirror = bit k: component k has data (total > 0), bit 4 + k: its root is a leaf
+    //   kd = base colour, kd[3] = front_refl_prob; ks = up, ks[3] = back_refl_prob
+    //   kt[k]    (uint bits) first word of component k, in 32-bit words from the start of the uv table
+    //   eta[k]   (uint bits) tensor tree: node count; Klems: row thetas | column thetas << 16
+    //   kappa[k] (uint bits) tensor tree: max depth; Klems: column patches
+    //   pad[0] = 0 (no texture); pad[6..7] = the uv table's address, written into the
+    //   shaded copy of the material on the device (bind_measured)
 };
 
 enum : int32_t { LIGHT_PLANE = 1, LIGHT_ENV = 2, LIGHT_POINT = 3, LIGHT_SPOT = 4, LIGHT_DIRECTIONAL = 5, LIGHT_SUN = 6,

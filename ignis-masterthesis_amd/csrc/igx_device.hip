@@ -793,7 +793,10 @@ __device__ __forceinline__ bool shade_step(const FrameArgs& fa, const SceneView&
     // writes its value at the hit; the basic one reads the table in place
     std::conditional_t<FULL, DevMaterial, const DevMaterial&> m = sv.mats[mat_id];
     if constexpr (FULL)
-        if (sv.uv) apply_texture(sv, m, hit_ent, hit_prim, hu, hv);
+        if (sv.uv) {
+            apply_texture(sv, m, hit_ent, hit_prim, hu, hv);
+            bind_measured(sv, m);
+        }
     sub_mark<CLK>(clk, 0); // surface element + material
     // on_hit (pathtracer.art:114-134)
     if (m.light >= 0 && s.entering) {
@@ -2134,7 +2137,10 @@ __global__ void __launch_bounds__(BLOCK) k_infobuffer(FrameArgs fa, SceneView sv
                 // the material as shade_step fetches it (a texture writes its value into a copy)
                 std::conditional_t<FULL, DevMaterial, const DevMaterial&> m = sv.mats[mat_id];
                 if constexpr (FULL)
-                    if (sv.uv) apply_texture(sv, m, hit_ent, hit_prim, hu, hv);
+                    if (sv.uv) {
+                        apply_texture(sv, m, hit_ent, hit_prim, hu, hv);
+                        bind_measured(sv, m);
+                    }
                 const f3 out_dir = neg(d);
                 if (!(ia.follow_specular && bsdf_is_specular<FULL>(m))) {
                     // on_hit (infobuffer.art:34-61): the albedo from 16 BSDF samples of a
@@ -2306,6 +2312,7 @@ struct igx_device {
     size_t table_bytes = 0;            // traversal tables (nodes, instances, triangles) of the current scene
     size_t shading_bytes = 0;          // shading tables (entities, vertices, normals, faces, materials, lights)
     size_t image_bytes = 0, cdf_bytes = 0; // image textures' texels and environment maps' sampling tables (in the uv table)
+    size_t measured_bytes = 0;             // measured BSDFs' words (in the uv table)
     int leaf_size = 4;
     // stream class of surviving paths (FrameArgs::classify; option "path_classes"):
     // paths inside a dielectric go to the back of their shard, so the next
@@ -3594,6 +3601,7 @@ extern "C" igx_status igx_upload_scene(igx_device* dev, const igx_scene_desc* de
                          t.fsh.size() * sizeof(t.fsh[0]);
     dev->image_bytes = t.image_bytes;
     dev->cdf_bytes = t.cdf_bytes;
+    dev->measured_bytes = t.measured_bytes;
     dev->cam_desc = desc->camera;
     dev->rays_w = desc->film_width;
     dev->rays_h = desc->film_height;
@@ -4875,6 +4883,7 @@ extern "C" igx_status igx_get_stats(igx_device* dev, igx_stats* out) {
     out->shading_bytes = dev->shading_bytes;
     out->image_bytes = dev->image_bytes;
     out->cdf_bytes = dev->cdf_bytes;
+    out->measured_bytes = dev->measured_bytes;
     out->slot_bytes = 0;
     for (const Slot& s : dev->slots)
         out->slot_bytes += (uint64_t)s.shard_cap * NSH * (2 * 56 * (s.pa.c_base ? 2 : 1) + 48 + (s.hb.h ? 20 : 0)) +

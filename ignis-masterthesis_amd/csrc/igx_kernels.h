@@ -2136,6 +2136,220 @@ __device__ __forceinline__ BsdfSample principled_sample(const DevMaterial& m, co
     return make_sample(in_dir, pdf, mulf(principled_eval(m, s, in_dir, out), 1 / pdf), s_eta);
 }
 
+// ---------------------------------------------------------------------------
+// Measured fenestration BSDFs: the tensor tree (bsdf/tensortree.art) and the
+// Klems matrix (bsdf/klems.art).  The material carries what the reference
+// compiles in as TensorTreeSpecification / KlemsSpecification (device_scene.h,
+// DevMaterial); the words of every component were checked by the host
+// (validate_measured) before they were uploaded, so each index below is formed
+// from counts that are known to lie inside the table.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ const uint32_t* measured_words(const DevMaterial& m) {
+    const uint64_t a = (uint64_t)__float_as_uint(m.pad[6]) | ((uint64_t)__float_as_uint(m.pad[7]) << 32);
+    return reinterpret_cast<const uint32_t*>(a);
+}
+// the table's address into the shaded copy of a measured material
+__device__ __forceinline__ void bind_measured(const SceneView& sv, DevMaterial& m) {
+    if (m.type != MAT_TENSORTREE && m.type != MAT_KLEMS) return;
+    const uint64_t a = reinterpret_cast<uint64_t>(sv.uv);
+    m.pad[6] = __uint_as_float((uint32_t)a);
+    m.pad[7] = __uint_as_float((uint32_t)(a >> 32));
+}
+// tt_transform_matrix(entering ? n : -n, up) (bsdf/tensortree.art:169-177, 195): columns
+// right, nup, normal, none of them normalised; the identity where up is parallel to the normal
+__device__ __forceinline__ Frame measured_frame(const DevMaterial& m, const Surface& s) {
+    const f3 n = s.entering ? s.local.n : neg(s.local.n);
+    const f3 right = cross(mk(m.ks[0], m.ks[1], m.ks[2]), n);
+    Frame f;
+    if (dot(right, right) <= FLT_EPS_) {
+        f.t = mk(1, 0, 0);
+        f.b = mk(0, 1, 0);
+        f.n = mk(0, 0, 1);
+    } else {
+        f.t = right;
+        f.b = cross(n, right);
+        f.n = n;
+    }
+    return f;
+}
+__device__ __forceinline__ float prodsign(float x, float y) { // core/common.art:93
+    return __uint_as_float(__float_as_uint(x) ^ (__float_as_uint(y) & 0x80000000u));
+}
+// concentric_disk_to_square (core/warp.art:24-40)
+__device__ __forceinline__ void concentric_disk_to_square(float px, float py, float& ox, float& oy) {
+    const bool quadrant = fabsf(px) > fabsf(py);
+    const float r_sign = quadrant ? px : py;
+    const float r = copysignf(sqrtf(px * px + py * py), r_sign);
+    const float phi = atan2f(prodsign(py, r_sign), prodsign(px, r_sign));
+    const float c = 4 * phi / PI_;
+    const float t = (quadrant ? c : 2 - c) * r;
+    ox = ((quadrant ? r : t) + 1) * 0.5f;
+    oy = ((quadrant ? t : r) + 1) * 0.5f;
+}
+// The one deliberate deviation from the reference: a coordinate is brought
+// into [0, 1) before it forms an index (concentric_disk_to_square can return
+// exactly 1, which there reads one value past the leaf)
+__device__ __forceinline__ float tt_unit(float p) { return fminf(fmaxf(p, 0.0f), 0.99999994f); }
+// tt_lookup_grid of one coordinate (bsdf/tensortree.art:38-49): the child bit, p becomes the rest
+__device__ __forceinline__ int tt_grid_bit(float& p) {
+    const float q = 2 * p;
+    const int t = q >= 1 ? 1 : 0;
+    p = q - (float)t;
+    return t;
+}
+// tt_eval_component (bsdf/tensortree.art:80-114) of component k
+__device__ __forceinline__ float tt_eval_component(const DevMaterial& m, int k, f3 in_dir, f3 out_dir) {
+    const uint32_t* const w = measured_words(m) + __float_as_uint(m.kt[k]);
+    const int node_count = (int)__float_as_uint(m.eta[k]);
+    const int max_depth = (int)__float_as_uint(m.kappa[k]);
+    const int32_t* const nodes = reinterpret_cast<const int32_t*>(w);
+    const float* const values = reinterpret_cast<const float*>(w + node_count);
+    const bool dim4 = m.dist == 4;
+    float ox, oy;
+    concentric_disk_to_square(out_dir.x, out_dir.y, ox, oy);
+    float p0, p1, p2, p3; // the reference's spos[4], in registers
+    if (!dim4) {
+        p0 = (0.5f - FLT_EPS_) - 0.5f * sqrtf(in_dir.x * in_dir.x + in_dir.y * in_dir.y);
+        p1 = ox;
+        p2 = oy;
+        p3 = 0;
+    } else {
+        concentric_disk_to_square(-in_dir.x, -in_dir.y, p0, p1);
+        p2 = ox;
+        p3 = oy;
+    }
+    p0 = tt_unit(p0);
+    p1 = tt_unit(p1);
+    p2 = tt_unit(p2);
+    p3 = tt_unit(p3);
+    int leaf = 0;
+    if (!((m.mirror >> (4 + k)) & 1)) {
+        // tt_climb_tree, bounded by the component's depth
+        int node = 0;
+        for (int d = 0; d < max_depth && node >= 0; ++d) {
+            int n = dim4 ? tt_grid_bit(p3) << 3 : 0;
+            n |= tt_grid_bit(p2) << 2;
+            n |= tt_grid_bit(p1) << 1;
+            n |= tt_grid_bit(p0);
+            node = nodes[node + n];
+        }
+        if (node >= 0) return 0; // not reached for a checked table
+        leaf = -node - 1;
+    }
+    const float leaf_value = values[leaf];
+    if (signbit(leaf_value)) return -leaf_value; // single-value leaf
+    // tt_lookup_leaf: the last coordinate is the lowest bit
+    int n;
+    if (dim4) n = (int)(2 * p3) + ((int)(2 * p2) << 1) + ((int)(2 * p1) << 2) + ((int)(2 * p0) << 3);
+    else n = (int)(2 * p2) + ((int)(2 * p1) << 1) + ((int)(2 * p0) << 2);
+    return values[leaf + n];
+}
+// TensorTreeModel::eval (bsdf/tensortree.art:146-165), wi and wo in the window's frame
+__device__ __forceinline__ float tensortree_eval(const DevMaterial& m, f3 wi, f3 wo) {
+    if (fabsf(wi.z) <= FLT_EPS_ || fabsf(wo.z) <= FLT_EPS_) return 0;
+    const bool in_front = wi.z >= 0, out_front = wo.z >= 0;
+    const f3 pwi = make_positive_hemi(wi), pwo = make_positive_hemi(wo);
+    float factor = 0;
+    if (in_front && out_front) {
+        if (m.mirror & 1) factor = tt_eval_component(m, 0, pwo, pwi);
+    } else if (in_front) {
+        if (m.mirror & 2) factor = tt_eval_component(m, 1, pwi, neg(pwo));
+    } else if (out_front) {
+        if (m.mirror & 8) factor = tt_eval_component(m, 3, pwo, neg(pwi));
+    } else {
+        if (m.mirror & 4) factor = tt_eval_component(m, 2, neg(pwo), neg(pwi));
+    }
+    return factor * fabsf(wi.z);
+}
+// k_index_of (bsdf/klems.art:49-67) in the basis at `b` with `thetas` bands:
+// spherical_from_dir, interval::binary_search with its final clamp, k_phi_index
+__device__ __forceinline__ int klems_index_of(const uint32_t* b, int thetas, f3 dir) {
+    const float theta = acosf(fminf(fmaxf(dir.z, -1.0f), 1.0f));
+    float phi = atan2f(dir.y, dir.x);
+    if (phi < 0) phi = phi + 2 * PI_;
+    int first = 0, len = thetas;
+    while (len > 0) {
+        const int half = len / 2, middle = first + half;
+        if (__uint_as_float(b[4 * middle + 1]) < theta) {
+            first = middle + 1;
+            len -= half + 1;
+        } else {
+            len = half;
+        }
+    }
+    const int i = clampi(first - 1, 0, thetas - 1);
+    const int phi_count = (int)b[4 * i + 3];
+    int j = max(0, (int)(phi * (float)phi_count * INV_PI_ / 2 + 0.5f));
+    if (j >= phi_count) j = 0;
+    return (int)b[4 * thetas + i] + j;
+}
+// k_eval_component (bsdf/klems.art:72-78) of component k: the matrix entry at
+// (row of out_dir, column of in_dir)
+__device__ __forceinline__ float klems_eval_component(const DevMaterial& m, int k, f3 in_dir, f3 out_dir) {
+    const uint32_t* const w = measured_words(m) + __float_as_uint(m.kt[k]);
+    const uint32_t tc = __float_as_uint(m.eta[k]);
+    const int rt = (int)(tc & 0xffffu), ct = (int)(tc >> 16);
+    const int cols = (int)__float_as_uint(m.kappa[k]);
+    const int in_idx = klems_index_of(w + 5 * rt, ct, in_dir);
+    const int out_idx = klems_index_of(w, rt, out_dir);
+    return __uint_as_float(w[5 * rt + 5 * ct + out_idx * cols + in_idx]);
+}
+// local_eval of make_klems_bsdf (bsdf/klems.art:189-202) without the colour; k_fi / k_fo / k_bi / k_bo (:44-47)
+__device__ __forceinline__ float klems_eval(const DevMaterial& m, f3 wi, f3 wo) {
+    const bool in_front = wi.z >= 0, out_front = wo.z >= 0;
+    float factor = 0;
+    if (in_front && out_front) {
+        if (m.mirror & 1) factor = klems_eval_component(m, 0, mk(-wo.x, -wo.y, wo.z), wi);
+    } else if (in_front) {
+        if (m.mirror & 2) factor = klems_eval_component(m, 1, wi, neg(wo));
+    } else if (out_front) {
+        if (m.mirror & 8) factor = klems_eval_component(m, 3, neg(wi), wo);
+    } else {
+        if (m.mirror & 4) factor = klems_eval_component(m, 2, neg(wo), mk(wi.x, wi.y, -wi.z));
+    }
+    return factor * fabsf(wi.z);
+}
+__device__ __forceinline__ float measured_eval_local(const DevMaterial& m, f3 wi, f3 wo) {
+    return m.type == MAT_KLEMS ? klems_eval(m, wi, wo) : tensortree_eval(m, wi, wo);
+}
+__device__ __forceinline__ f3 measured_eval(const DevMaterial& m, const Surface& s, f3 in, f3 out) {
+    const Frame f = measured_frame(m, s);
+    return mulf(mk(m.kd[0], m.kd[1], m.kd[2]), measured_eval_local(m, to_local(f, in), to_local(f, out)));
+}
+// pdf of make_tensortree_bsdf / make_klems_bsdf (bsdf/tensortree.art:205-213)
+__device__ __forceinline__ float measured_pdf(const DevMaterial& m, const Surface& s, f3 in, f3 out) {
+    const Frame f = measured_frame(m, s);
+    const f3 wo = to_local(f, out), wi = to_local(f, in);
+    const float refl_prob = wo.z >= 0 ? m.kd[3] : m.ks[3];
+    const float prob = same_hemi(wo, wi) ? refl_prob : 1 - refl_prob;
+    return prob * (fabsf(wi.z) / PI_);
+}
+// sample of both (bsdf/tensortree.art:214-235; the live sampler of bsdf/klems.art:256-276):
+// cosine hemisphere, the side by a third number that is drawn only if refl_prob > 0
+__device__ __forceinline__ BsdfSample measured_sample(const DevMaterial& m, const Surface& s, Rng& rnd, f3 out) {
+    const Frame f = measured_frame(m, s);
+    const f3 wo = to_local(f, out);
+    const float u = rnd.next_f32();
+    const float v = rnd.next_f32();
+    float cpdf;
+    const f3 sd = sample_cosine_hemisphere(u, v, &cpdf);
+    if (cpdf <= FLT_EPS_) return reject_sample();
+    const float refl_prob = wo.z >= 0 ? m.kd[3] : m.ks[3];
+    f3 wi;
+    float prob;
+    if (refl_prob > 0 && rnd.next_f32() < refl_prob) {
+        wi = make_same_hemi(wo, sd);
+        prob = refl_prob;
+    } else {
+        wi = neg(make_same_hemi(wo, sd));
+        prob = 1 - refl_prob;
+    }
+    const float e_pdf = prob * cpdf;
+    if (e_pdf <= FLT_EPS_) return reject_sample();
+    const float e = measured_eval_local(m, wi, wo) / e_pdf;
+    return make_sample(frame_to_world(f, wi), e_pdf, mulf(mk(m.kd[0], m.kd[1], m.kd[2]), e), 1);
+}
+
 // FULL = false compiles only the materials and lights of the basic set
 // (Lambert diffuse, dielectric; plane/env/point/spot/directional/sun lights):
 // the upload picks that kernel variant when the scene needs nothing more, so
@@ -2150,6 +2364,8 @@ __device__ __forceinline__ f3 bsdf_eval(const DevMaterial& m, const Surface& s, 
     switch (m.type) {
     case MAT_DIFFUSE: return diffuse_eval(m, s, in, out);
     case MAT_PRINCIPLED: return principled_eval(m, s, in, out);
+    case MAT_TENSORTREE:
+    case MAT_KLEMS: return measured_eval(m, s, in, out);
     case MAT_CONDUCTOR: return m.dist == MF_DELTA ? mk(0, 0, 0) : rough_conductor_eval(m, s, in, out);
     case MAT_PLASTIC: {
         float k = plastic_mix(m, s, out);
@@ -2165,6 +2381,8 @@ __device__ __forceinline__ float bsdf_pdf(const DevMaterial& m, const Surface& s
     switch (m.type) {
     case MAT_DIFFUSE: return diffuse_pdf(s, in);
     case MAT_PRINCIPLED: return principled_pdf(m, s, in, out);
+    case MAT_TENSORTREE:
+    case MAT_KLEMS: return measured_pdf(m, s, in, out);
     case MAT_CONDUCTOR: return m.dist == MF_DELTA ? 0.0f : rough_conductor_pdf(m, s, in, out);
     case MAT_PLASTIC: {
         float k = plastic_mix(m, s, out);
@@ -2213,6 +2431,8 @@ __device__ __forceinline__ BsdfSample bsdf_sample(const DevMaterial& m, const Su
     case MAT_DIELECTRIC: return dielectric_sample(m, s, rnd, out);
     case MAT_CONDUCTOR: return specular_lobe_sample(m, s, rnd, out);
     case MAT_PRINCIPLED: return principled_sample(m, s, rnd, out);
+    case MAT_TENSORTREE:
+    case MAT_KLEMS: return measured_sample(m, s, rnd, out);
     default: break;
     }
     // plastic: make_variadic_mix_bsdf(diffuse_extra, specular, mix_f).sample (bsdf/mix.art:29-62)

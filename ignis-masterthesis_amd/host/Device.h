@@ -211,10 +211,11 @@ public:
         qty("BounceRays", mStats.bounce_rays);
         qty("PrimaryRays", mStats.camera_rays + mStats.bounce_rays);
         qty("TotalRays", mStats.camera_rays + mStats.bounce_rays + mStats.shadow_rays);
-        if (mStats.image_bytes || mStats.cdf_bytes) {
-            char b[160];
-            std::snprintf(b, sizeof(b), "  Image textures:\n  |-%-12s %llu bytes\n  |-%-12s %llu bytes\n", "Texels",
-                          (unsigned long long)mStats.image_bytes, "EnvCDF", (unsigned long long)mStats.cdf_bytes);
+        if (mStats.image_bytes || mStats.cdf_bytes || mStats.measured_bytes) {
+            char b[224];
+            std::snprintf(b, sizeof(b), "  Image textures:\n  |-%-12s %llu bytes\n  |-%-12s %llu bytes\n  |-%-12s %llu bytes\n", "Texels",
+                          (unsigned long long)mStats.image_bytes, "EnvCDF", (unsigned long long)mStats.cdf_bytes, "MeasuredBSDF",
+                          (unsigned long long)mStats.measured_bytes);
             out += b;
         }
         return out;
@@ -477,6 +478,7 @@ private:
         std::vector<igx_image> images; // headers and texel addresses: texels behind an unchanged address count as
                                        // unchanged (igx_shading_view in igx_scene.h states the rule)
         std::vector<igx_texture> textures;
+        std::vector<igx_measured> measured; // as the images: the words behind an unchanged address count as unchanged
         void take(const igx_shading_view& v) {
             valid = true;
             film_width = v.film_width;
@@ -486,6 +488,16 @@ private:
             lights.assign(v.lights, v.lights + v.num_lights);
             images.assign(v.images, v.images + v.num_images);
             textures.assign(v.textures, v.textures + v.num_textures);
+            measured.assign(v.measured, v.measured + v.num_measured);
+        }
+        bool same_measured(const igx_shading_view& v) const {
+            for (size_t i = 0; i < measured.size(); ++i) {
+                const igx_measured &a = measured[i], &b = v.measured[i];
+                if (a.kind != b.kind || a.num_words != b.num_words || a.words != b.words ||
+                    std::memcmp(a.component, b.component, sizeof(a.component)) != 0)
+                    return false;
+            }
+            return true;
         }
         // field by field: igx_image has padding bytes, whose content says nothing
         bool same_images(const igx_shading_view& v) const {
@@ -499,7 +511,7 @@ private:
             return valid && film_width == v.film_width && film_height == v.film_height &&
                    std::memcmp(&technique, &v.technique, sizeof(technique)) == 0 && materials.size() == v.num_materials &&
                    lights.size() == v.num_lights && images.size() == v.num_images && textures.size() == v.num_textures &&
-                   same_images(v) &&
+                   same_images(v) && measured.size() == v.num_measured && same_measured(v) &&
                    (textures.empty() || std::memcmp(textures.data(), v.textures, textures.size() * sizeof(igx_texture)) == 0) &&
                    (materials.empty() || std::memcmp(materials.data(), v.materials, materials.size() * sizeof(igx_material)) == 0) &&
                    (lights.empty() || std::memcmp(lights.data(), v.lights, lights.size() * sizeof(igx_light)) == 0);

@@ -259,6 +259,17 @@ static void build_from_tables(SceneStore& S, const igx_database_view& db, const 
     for (const igx_material& m : S.materials)
         if (m.texture == IGX_TEXTURE_IMAGE && (m.tex_index < 0 || (uint32_t)m.tex_index >= sh.num_textures))
             fail("materials: texture index beyond the texture table");
+    // measured BSDFs: the words are copied, the indices checked (build_scene_tables checks the tables)
+    if (sh.num_measured && !sh.measured) fail("measured bsdfs: null table");
+    for (uint32_t i = 0; i < sh.num_measured; ++i) {
+        const igx_measured& md = sh.measured[i];
+        if (md.num_words && !md.words) fail("measured bsdfs: null word array");
+        S.measured_words.emplace_back(md.words, md.words + md.num_words);
+        S.measured.push_back(md);
+    }
+    for (const igx_material& m : S.materials)
+        if ((m.bsdf_type == IGX_BSDF_TENSORTREE || m.bsdf_type == IGX_BSDF_KLEMS) && (m.measured < 0 || (uint32_t)m.measured >= sh.num_measured))
+            fail("materials: index beyond the measured bsdf table");
     S.desc.film_width = sh.film_width;
     S.desc.film_height = sh.film_height;
     S.desc.camera = sh.camera;

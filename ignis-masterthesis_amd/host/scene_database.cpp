@@ -205,6 +205,8 @@ void serialize_scene(const igx_scene_desc& desc, SceneDatabase& db, igx_shading_
     shading.images = desc.images;
     shading.num_textures = desc.num_textures;
     shading.textures = desc.textures;
+    shading.num_measured = desc.num_measured;
+    shading.measured = desc.measured;
 }
 
 } // namespace IG

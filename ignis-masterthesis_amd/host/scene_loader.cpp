@@ -14,6 +14,7 @@
 #include "scene_store.h"
 #include "cie_sky.h"
 #include "image_io.h"
+#include "measured_bsdf.h"
 #include "sun_position.h"
 
 #include <cctype>
@@ -656,6 +657,7 @@ static void build_scene(SceneStore& S, const Value& doc, const std::string& base
     };
 
     // ---- bsdfs ----
+    std::unordered_map<std::string, int32_t> measured_ids; // measured BSDF files already loaded
     std::unordered_map<std::string, igx_material> bsdfs;
     if (const Value* arr = array_of(doc, "bsdfs")) {
         for (auto& b : arr->arr) {
@@ -665,6 +667,8 @@ static void build_scene(SceneStore& S, const Value& doc, const std::string& base
             igx_material m{};
             m.light = -1;
             m.tex_index = -1;
+            m.measured = -1;
+            m.up[2] = 1.0f;
             m.ext_ior = 1.0f;
             m.int_ior = 1.5046f;
             m.kd[0] = m.kd[1] = m.kd[2] = 0.8f;
@@ -747,6 +751,32 @@ static void build_scene(SceneStore& S, const Value& doc, const std::string& base
                 m.clearcoat_roughness = bp.number("clearcoat_roughness", 0.1f);
                 m.thin = bp.boolean("thin", false) ? 1 : 0;
                 m.clearcoat_top_only = bp.boolean("clearcoat_top_only", true) ? 1 : 0;
+            } else if (type == "tensortree" || type == "klems") {
+                // TensorTreeBSDF::serialize / KlemsBSDF::serialize: one loaded file per path
+                // (the reference's "_tt_" / "_klems_" export cache), base_color and up
+                const bool klems = type == "klems";
+                m.bsdf_type = klems ? IGX_BSDF_KLEMS : IGX_BSDF_TENSORTREE;
+                if (!bp.has("filename")) fail("bsdf '" + name + "': no filename");
+                const Value* obj_dir = b.find("__base_dir");
+                const std::string file = join_path(obj_dir && obj_dir->is_string() ? obj_dir->str : base_dir, bp.string("filename"));
+                const std::string key = (klems ? "_klems_" : "_tt_") + file;
+                auto known = measured_ids.find(key);
+                if (known == measured_ids.end()) {
+                    igx::MeasuredData md;
+                    std::string err;
+                    if (!igx::load_measured_file(file, klems ? IGX_MEASURED_KLEMS : IGX_MEASURED_TENSORTREE, md, err))
+                        fail("bsdf '" + name + "': " + err);
+                    S.measured.push_back(md.m);
+                    S.measured_words.push_back(std::move(md.words));
+                    known = measured_ids.emplace(key, (int32_t)S.measured.size() - 1).first;
+                }
+                m.measured = known->second;
+                V3 base = bp.color("base_color", V3(1, 1, 1));
+                m.kd[0] = base.x; m.kd[1] = base.y; m.kd[2] = base.z;
+                V3 up = bp.vec3("up", V3(0, 0, 1));
+                const float ul = std::sqrt(up.x * up.x + up.y * up.y + up.z * up.z);
+                if (ul > 0) up = V3(up.x / ul, up.y / ul, up.z / ul); // Eigen's normalized(): a zero vector stays
+                m.up[0] = up.x; m.up[1] = up.y; m.up[2] = up.z;
             } else {
                 fail("bsdf '" + name + "': unsupported bsdf type '" + type + "'");
             }

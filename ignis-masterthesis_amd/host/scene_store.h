@@ -25,6 +25,9 @@ struct SceneStore {
     std::vector<std::vector<uint8_t>> image_pixels;
     std::vector<igx_image> images;
     std::vector<igx_texture> textures;
+    // measured BSDFs: the words of measured[i] are measured_words[i]
+    std::vector<std::vector<uint32_t>> measured_words;
+    std::vector<igx_measured> measured;
     // names (JSON loader only): entity names, and per material id its BSDF
     // name and emissive entity (LoaderContext::Material, LoaderContext.h:19-27)
     std::vector<std::string> entity_names;
@@ -47,6 +50,12 @@ struct SceneStore {
         desc.images = images.data();
         desc.num_textures = (uint32_t)textures.size();
         desc.textures = textures.data();
+        for (size_t i = 0; i < measured.size(); ++i) {
+            measured[i].num_words = (uint32_t)measured_words[i].size();
+            measured[i].words = measured_words[i].data();
+        }
+        desc.num_measured = (uint32_t)measured.size();
+        desc.measured = measured.data();
     }
 };
 

@@ -4,6 +4,7 @@
 #include "env_cdf.h"
 
 #include "cie_sky.h"
+#include "measured_bsdf.h"
 
 #include <algorithm>
 #include <array>
@@ -651,6 +652,24 @@ igx_status build_scene_tables(const igx_scene_desc& desc, const SceneBuildOption
             std::memcpy(lights[light_remap[l]].radiance, &e, sizeof(e));
         }
     }
+    // Measured BSDFs: every table is checked, then its words go behind whatever the
+    // uv table holds so far; a material names its components by word offsets
+    std::vector<uint32_t> measured_at(desc.num_measured, 0); // in 32-bit words from the start of uvs
+    if (desc.num_measured) {
+        if (!desc.measured) return fail(IGX_ERR_INVALID_ARGUMENT, "null measured bsdf table");
+        for (uint32_t i = 0; i < desc.num_measured; ++i) {
+            std::string err;
+            if (!validate_measured(desc.measured[i], err)) return fail(IGX_ERR_INVALID_ARGUMENT, err);
+        }
+        for (uint32_t i = 0; i < desc.num_measured; ++i) {
+            const igx_measured& md = desc.measured[i];
+            if (uvs.size() + (md.num_words + 1) / 2 > 0x3fffffffu) return fail(IGX_ERR_UNSUPPORTED, "uv table and measured bsdfs exceed 8 GB");
+            measured_at[i] = (uint32_t)(2 * uvs.size());
+            uvs.resize(uvs.size() + ((size_t)md.num_words + 1) / 2, Float2{0, 0});
+            if (md.num_words) std::memcpy(reinterpret_cast<uint8_t*>(uvs.data()) + 4 * (size_t)measured_at[i], md.words, 4 * (size_t)md.num_words);
+            out.measured_bytes += 4 * (size_t)md.num_words;
+        }
+    }
     auto& mats = out.mats;
     mats.resize(desc.num_materials);
     for (uint32_t i = 0; i < desc.num_materials; ++i) {
@@ -662,6 +681,8 @@ igx_status build_scene_tables(const igx_scene_desc& desc, const SceneBuildOption
         case IGX_BSDF_CONDUCTOR: d.type = MAT_CONDUCTOR; break;
         case IGX_BSDF_PLASTIC: d.type = MAT_PLASTIC; break;
         case IGX_BSDF_PRINCIPLED: d.type = MAT_PRINCIPLED; break;
+        case IGX_BSDF_TENSORTREE: d.type = MAT_TENSORTREE; break;
+        case IGX_BSDF_KLEMS: d.type = MAT_KLEMS; break;
         default: return fail(IGX_ERR_UNSUPPORTED, "unsupported bsdf type " + std::to_string(m.bsdf_type));
         }
         if (m.distribution < IGX_MICROFACET_DELTA || m.distribution > IGX_MICROFACET_BECKMANN)
@@ -700,6 +721,43 @@ igx_status build_scene_tables(const igx_scene_desc& desc, const SceneBuildOption
             std::memcpy(&d.pad[7], &tex_record_at[m.tex_index], 4);
         } else if (m.texture != IGX_TEXTURE_NONE) {
             return fail(IGX_ERR_UNSUPPORTED, "texture " + std::to_string(m.texture) + " on this bsdf type");
+        }
+        if (m.bsdf_type == IGX_BSDF_TENSORTREE || m.bsdf_type == IGX_BSDF_KLEMS) {
+            // packing of a measured BSDF (device_scene.h, DevMaterial)
+            if (m.measured < 0 || (uint32_t)m.measured >= desc.num_measured)
+                return fail(IGX_ERR_INVALID_ARGUMENT, "material " + std::to_string(i) + ": index beyond the measured bsdf table");
+            const igx_measured& md = desc.measured[m.measured];
+            const bool tree = m.bsdf_type == IGX_BSDF_TENSORTREE;
+            if (md.kind != (tree ? IGX_MEASURED_TENSORTREE : IGX_MEASURED_KLEMS))
+                return fail(IGX_ERR_INVALID_ARGUMENT, "material " + std::to_string(i) + ": measured bsdf of the other kind");
+            if (m.texture != IGX_TEXTURE_NONE) return fail(IGX_ERR_UNSUPPORTED, "texture on a measured bsdf");
+            for (int c = 0; c < 3; ++c)
+                if (!std::isfinite(m.up[c])) return fail(IGX_ERR_INVALID_ARGUMENT, "material " + std::to_string(i) + ": up is not finite");
+            DevMaterial q{};
+            q.type = d.type;
+            q.light = d.light;
+            q.dist = tree ? md.component[0].ndim : 0;
+            const float fr = md.component[IGX_MEASURED_FRONT_REFLECTION].total, ft = md.component[IGX_MEASURED_FRONT_TRANSMISSION].total;
+            const float br = md.component[IGX_MEASURED_BACK_REFLECTION].total, bt = md.component[IGX_MEASURED_BACK_TRANSMISSION].total;
+            auto sdiv = [](float a, float b) { return std::fabs(b) <= 1.1920928955e-07f ? 0.0f : a / b; }; // safe_div
+            for (int c = 0; c < 3; ++c) {
+                q.kd[c] = m.kd[c];
+                q.ks[c] = m.up[c];
+            }
+            q.kd[3] = sdiv(fr, fr + bt); // front_refl_prob (bsdf/tensortree.art:187-188)
+            q.ks[3] = sdiv(br, br + ft); // back_refl_prob
+            for (int k = 0; k < 4; ++k) {
+                const igx_measured_component& mc = md.component[k];
+                if (mc.total > 0) q.mirror |= 1 << k;
+                if (tree && mc.root_is_leaf) q.mirror |= 16 << k;
+                const uint32_t at = measured_at[m.measured] + mc.offset;
+                const uint32_t a = tree ? mc.node_count : (mc.theta_count[0] | (mc.theta_count[1] << 16));
+                const uint32_t b = tree ? (uint32_t)mc.max_depth : mc.entry_count[1];
+                std::memcpy(&q.kt[k], &at, 4);
+                std::memcpy(&q.eta[k], &a, 4);
+                std::memcpy(&q.kappa[k], &b, 4);
+            }
+            d = q;
         }
         if (m.bsdf_type == IGX_BSDF_PRINCIPLED) {
             // packing of the principled closure (igx_kernels.h, principled_of)
@@ -760,6 +818,7 @@ igx_status build_scene_tables(const igx_scene_desc& desc, const SceneBuildOption
     for (uint32_t i = 0; i < desc.num_materials; ++i) {
         const igx_material& m = desc.materials[i];
         if (m.bsdf_type == IGX_BSDF_CONDUCTOR || m.bsdf_type == IGX_BSDF_PLASTIC || m.bsdf_type == IGX_BSDF_PRINCIPLED ||
+            m.bsdf_type == IGX_BSDF_TENSORTREE || m.bsdf_type == IGX_BSDF_KLEMS ||
             (m.bsdf_type == IGX_BSDF_DIFFUSE && m.diffuse_alpha > 1.1920929e-7f))
             out.full_shading = true;
     }

@@ -55,7 +55,8 @@ struct SceneTables {
     std::vector<Float4> vtx, nrm; // mesh vertices and vertex normals (object space)
     std::vector<Int4> idx;       // faces: local vertex indices
     std::vector<Float2> uvs;     // texture coordinates, only for scenes with a textured material; behind
-                                 // them the image textures' records and texels (igxd::TexRecord)
+                                 // them the image textures' records and texels (igxd::TexRecord), the
+                                 // environment maps' sampling tables and the measured BSDFs' words
     std::vector<Float4> fsh;     // per face: vertex normals and indices in one record (SceneView::fsh)
     std::vector<Float4> fn_tab;  // world-space unit face normals (surface_element)
     std::vector<int32_t> ent_fn; // per entity: first face-normal entry, -1 without a table
@@ -79,6 +80,7 @@ struct SceneTables {
     bool textured = false;       // a material carries a texture
     size_t image_bytes = 0;      // texels of the image textures in uvs
     size_t cdf_bytes = 0;        // sampling tables of the image environment maps in uvs
+    size_t measured_bytes = 0;   // words of the measured BSDFs in uvs
 };
 
 // Build every table of `desc`.  On failure the status and `error` are what

@@ -44,7 +44,7 @@ class Material(C.Structure):
                 ("sheen_tint", C.c_float), ("clearcoat", C.c_float), ("clearcoat_gloss", C.c_float),
                 ("clearcoat_roughness", C.c_float), ("clearcoat_top_only", C.c_int32),
                 ("texture", C.c_int32), ("tex_scale", C.c_float), ("tex_kd1", C.c_float * 3),
-                ("tex_index", C.c_int32)]
+                ("tex_index", C.c_int32), ("measured", C.c_int32), ("up", C.c_float * 3)]
 
 
 # igx_material.texture
@@ -62,6 +62,23 @@ class Image(C.Structure):
 class Texture(C.Structure):
     _fields_ = [("image", C.c_int32), ("filter", C.c_int32), ("wrap_u", C.c_int32), ("wrap_v", C.c_int32),
                 ("transform", C.c_float * 6)]
+
+
+# igx_material.bsdf_type of the measured fenestration BSDFs, igx_measured.kind and the component order
+BSDF_TENSORTREE, BSDF_KLEMS = 5, 6
+MEASURED_TENSORTREE, MEASURED_KLEMS = range(2)
+MEASURED_FRONT_REFLECTION, MEASURED_FRONT_TRANSMISSION, MEASURED_BACK_REFLECTION, MEASURED_BACK_TRANSMISSION = range(4)
+
+
+class MeasuredComponent(C.Structure):
+    _fields_ = [("total", C.c_float), ("offset", C.c_uint32), ("ndim", C.c_int32), ("node_count", C.c_uint32),
+                ("value_count", C.c_uint32), ("root_is_leaf", C.c_int32), ("max_depth", C.c_int32),
+                ("theta_count", C.c_uint32 * 2), ("entry_count", C.c_uint32 * 2)]
+
+
+class Measured(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("component", MeasuredComponent * 4), ("num_words", C.c_uint32),
+                ("words", C.POINTER(C.c_uint32))]
 
 
 # igx_light.type (include/igx_scene.h)
@@ -110,7 +127,8 @@ class SceneDesc(C.Structure):
                 ("num_lights", C.c_uint32), ("lights", C.POINTER(Light)),
                 ("scene_bbox_min", C.c_float * 3), ("scene_bbox_max", C.c_float * 3),
                 ("num_images", C.c_uint32), ("images", C.POINTER(Image)),
-                ("num_textures", C.c_uint32), ("textures", C.POINTER(Texture))]
+                ("num_textures", C.c_uint32), ("textures", C.POINTER(Texture)),
+                ("num_measured", C.c_uint32), ("measured", C.POINTER(Measured))]
 
 
 class LookupEntry(C.Structure):
@@ -133,7 +151,8 @@ class ShadingView(C.Structure):
                 ("num_materials", C.c_uint32), ("materials", C.POINTER(Material)),
                 ("num_lights", C.c_uint32), ("lights", C.POINTER(Light)),
                 ("num_images", C.c_uint32), ("images", C.POINTER(Image)),
-                ("num_textures", C.c_uint32), ("textures", C.POINTER(Texture))]
+                ("num_textures", C.c_uint32), ("textures", C.POINTER(Texture)),
+                ("num_measured", C.c_uint32), ("measured", C.POINTER(Measured))]
 
 
 # ---- igx.h ----------------------------------------------------------------
@@ -173,7 +192,8 @@ class Stats(C.Structure):
                 ("hot_node_visits", C.c_uint64 * 3), ("extend_class_shade_cycles", C.c_uint64 * 16),
                 ("shadow_class_rays", C.c_uint64 * 2),
                 ("lds_shading_bytes", C.c_int32), ("extend_block_threads", C.c_int32),
-                ("launches_extend_shaped", C.c_uint64 * 2), ("image_bytes", C.c_uint64), ("cdf_bytes", C.c_uint64)]
+                ("launches_extend_shaped", C.c_uint64 * 2), ("image_bytes", C.c_uint64), ("cdf_bytes", C.c_uint64),
+                ("measured_bytes", C.c_uint64)]
 
     def as_dict(self):
         return {name: (list(getattr(self, name)) if isinstance(getattr(self, name), C.Array) else getattr(self, name))

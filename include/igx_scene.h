@@ -79,7 +79,9 @@ enum {
     IGX_BSDF_DIELECTRIC = 1, /* pure (smooth) dielectric (bsdf/dielectric.art) */
     IGX_BSDF_CONDUCTOR  = 2, /* mirror / pure / rough conductor (bsdf/conductor.art) */
     IGX_BSDF_PLASTIC    = 3, /* Fresnel mix of diffuse and a conductor lobe (bsdf/plastic.art) */
-    IGX_BSDF_PRINCIPLED = 4  /* Disney BSDF (bsdf/principled.art) */
+    IGX_BSDF_PRINCIPLED = 4, /* Disney BSDF (bsdf/principled.art) */
+    IGX_BSDF_TENSORTREE = 5, /* measured tensor tree BSDF of a fenestration (bsdf/tensortree.art) */
+    IGX_BSDF_KLEMS      = 6  /* measured Klems matrix BSDF of a fenestration (bsdf/klems.art) */
 };
 /* microfacet distribution of conductor / plastic lobes (BSDF::setupRoughness, BSDF.cpp:53-99) */
 enum { IGX_MICROFACET_DELTA = 0, IGX_MICROFACET_VNDF_GGX = 1, IGX_MICROFACET_GGX = 2, IGX_MICROFACET_BECKMANN = 3 };
@@ -115,6 +117,13 @@ typedef struct igx_material {
      * image texture `tex_index` of igx_scene_desc::textures at the surface's
      * texture coordinates; -1 (or 0 with another `texture`) otherwise */
     int32_t tex_index;
+    /* IGX_BSDF_TENSORTREE / IGX_BSDF_KLEMS (TensorTreeBSDF.cpp, KlemsBSDF.cpp): kd =
+     * base_color (default 1), `measured` the index into igx_scene_desc::measured,
+     * `up` the unit up vector of the window's own frame (default +Z); the frame is
+     * tt_transform_matrix(unflipped normal, up), the identity where up is
+     * parallel to the normal (bsdf/tensortree.art:169-177).  Unused otherwise. */
+    int32_t measured;
+    float up[3];
 } igx_material;
 
 enum { IGX_TEXTURE_NONE = 0, IGX_TEXTURE_CHECKER = 1, IGX_TEXTURE_IMAGE = 2 };
@@ -142,6 +151,55 @@ typedef struct igx_texture {
     int32_t wrap_u, wrap_v;/* IGX_WRAP_*, "wrap_mode" or "wrap_mode_u" / "wrap_mode_v", default repeat */
     float transform[6];    /* 2x3 row-major: uv' = transform * (u, v, 1) (LoaderUtils::inlineTransformAs2d) */
 } igx_texture;
+
+/* ---- measured fenestration BSDFs ------------------------------------------ */
+/* One Radiance BSDF XML file after the reference's loaders
+ * (measured/TensorTreeLoader.cpp, measured/KlemsLoader.cpp): four components in
+ * the order below, after the loaders' front / back renaming, and one array of
+ * 32-bit words they point into.  Two components may share their words (the
+ * transmission of a file that gives only one side).  The word layout is igx's
+ * own:
+ *  - tensor tree component at `offset`: node_count int32 node values, then
+ *    value_count floats.  Nodes come in groups of 2^ndim child slots, the
+ *    root's group first, every child group behind its parent's
+ *    (TensorTreeComponent::addNode).  A node value >= 0 is the index of the
+ *    child's group (a multiple of 2^ndim); a value < 0 names the leaf whose
+ *    values start at -(value + 1).  A leaf is one value with the sign bit set
+ *    (its magnitude counts) or 2^ndim values.  root_is_leaf: no nodes, the leaf
+ *    at value 0.  max_depth: the most node groups a lookup passes (0 for a
+ *    root leaf), at most 16.
+ *  - Klems component at `offset`: the row (outgoing) basis as theta_count[0]
+ *    records (float centre, lower, upper theta in radians, uint32 phi count),
+ *    ascending in upper theta, then theta_count[0] uint32 first-patch numbers;
+ *    the column (incoming) basis likewise with theta_count[1]; then the
+ *    matrix, entry_count[0] x entry_count[1] floats, row-major.  A component
+ *    without data has all four counts 0 and total 0.
+ * `total` steers only the choice between reflection and transmission when
+ * sampling (TensorTreeNode::computeTotal, KlemsComponent::computeTotal); a
+ * component with total <= 0 is never evaluated. */
+enum { IGX_MEASURED_TENSORTREE = 0, IGX_MEASURED_KLEMS = 1 };
+enum {
+    IGX_MEASURED_FRONT_REFLECTION = 0, IGX_MEASURED_FRONT_TRANSMISSION = 1, IGX_MEASURED_BACK_REFLECTION = 2,
+    IGX_MEASURED_BACK_TRANSMISSION = 3
+};
+typedef struct igx_measured_component {
+    float total;
+    uint32_t offset;         /* first word of the component in igx_measured::words */
+    /* tensor tree (zero for Klems) */
+    int32_t ndim;            /* 3 or 4, the same in all four components */
+    uint32_t node_count, value_count;
+    int32_t root_is_leaf;
+    int32_t max_depth;
+    /* Klems (zero for a tensor tree): [0] rows = outgoing, [1] columns = incoming */
+    uint32_t theta_count[2];
+    uint32_t entry_count[2];
+} igx_measured_component;
+typedef struct igx_measured {
+    int32_t kind;            /* IGX_MEASURED_* */
+    igx_measured_component component[4]; /* IGX_MEASURED_FRONT_REFLECTION ... */
+    uint32_t num_words;
+    const uint32_t* words;
+} igx_measured;
 
 /* ---- lights ------------------------------------------------------------ */
 enum {
@@ -247,6 +305,7 @@ typedef struct igx_scene_desc {
     float scene_bbox_min[3], scene_bbox_max[3];
     uint32_t num_images;    const igx_image* images;
     uint32_t num_textures;  const igx_texture* textures;
+    uint32_t num_measured;  const igx_measured* measured; /* igx_material::measured */
 } igx_scene_desc;
 
 /* ---- loader C-ABI (stand-in for the reference's Loader, src/runtime/loader) */
@@ -377,6 +436,10 @@ typedef struct igx_shading_view {
      * a new buffer. */
     uint32_t num_images;    const igx_image* images;
     uint32_t num_textures;  const igx_texture* textures;
+    /* measured BSDFs of the materials (igx_material::measured); the words are
+     * copied.  The rule for a view handed over again is that of the images: a
+     * table counts as changed if its counts or its `words` address changed. */
+    uint32_t num_measured;  const igx_measured* measured;
 } igx_shading_view;
 
 /* Build a scene from the reference's tables plus the shading view.  Plane
