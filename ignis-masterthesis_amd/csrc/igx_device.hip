@@ -63,9 +63,11 @@ using namespace igxd;
 //   (igx_post.h); 7 = the wide k_extend's generate and bounce shapes
 //   (host/extend_shape.h); 8, 9 = the two shapes of the BLOCK-thread k_extend
 //   with LDS-staged and with global tables; 10 = k_camera_rays (igx_camera_rays).
-//   Types and device functions are shared; each
-//   part instantiates only its own launch helpers (explicit instantiation),
-//   the others see them as extern templates.
+//   Types and device functions are shared.  A part instantiates a kernel by
+//   taking its address, in the choosers it defines under its #if IGX_PART == n
+//   (plain functions declared for all parts: "Which instantiation a launch
+//   runs", below); part 0 launches, sizes grids and raises LDS limits through
+//   what they return and takes no such address itself.
 #ifndef IGX_PART
 #define IGX_PART 0
 #endif
@@ -2676,133 +2678,206 @@ inline SceneView launch_view(const igx_device* dev, const LaunchCtx& ctx, int* s
     return sv;
 }
 
-// Launch helpers dispatching on the scene's traversal variant.
-// (bit 7, VARIANT_Q4: quantised 4-wide nodes, only with bit 1)
-#define IGX_DISPATCH_VARIANT(v, MACRO)        \
-    do {                                      \
-        switch ((v) & (3 | VARIANT_Q4)) {     \
-        case 0: MACRO(0); break;              \
-        case 1: MACRO(1); break;              \
-        case 2: MACRO(2); break;              \
-        case 3: MACRO(3); break;              \
-        case 2 | VARIANT_Q4: MACRO(130); break; \
-        default: MACRO(131); break;           \
-        }                                     \
-    } while (0)
-// shading kernels also dispatch on the material/light feature bit
-#define IGX_DISPATCH_VARIANT8(v, MACRO)       \
-    do {                                      \
-        switch ((v) & (7 | VARIANT_Q4)) {     \
-        case 0: MACRO(0); break;              \
-        case 1: MACRO(1); break;              \
-        case 2: MACRO(2); break;              \
-        case 3: MACRO(3); break;              \
-        case 4: MACRO(4); break;              \
-        case 5: MACRO(5); break;              \
-        case 6: MACRO(6); break;              \
-        case 7: MACRO(7); break;              \
-        case 2 | VARIANT_Q4: MACRO(130); break; \
-        case 3 | VARIANT_Q4: MACRO(131); break; \
-        case 6 | VARIANT_Q4: MACRO(134); break; \
-        default: MACRO(135); break;           \
-        }                                     \
-    } while (0)
-
-// The wide k_extend (BLOCK_WIDE threads, shading tables staged behind the
-// traversal tables): its launch, its resident blocks per CU and the
-// one-time raise of its dynamic-LDS limit (a block above 64 KB needs it).
-template <bool STATS>
-void launch_extend_wide(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in,
-                        const PathBuf& out, const KernelCounters& kc, int tail) {
-    const size_t dyn = lds_pad16(dev->lds_scene_bytes) + dev->lds_shading_bytes;
-    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
-#define L_EXTW(S) hipLaunchKernelGGL((k_extend<S, STATS, true, BLOCK_WIDE>), dim3(grid), dim3(BLOCK_WIDE), dyn, ctx.main, fa, sv, in, out, s.sh, s.L, kc, tail)
-    IGX_DISPATCH_VARIANT8(dev->variant, L_EXTW);
-#undef L_EXTW
-}
-template <typename K>
-hipError_t raise_dynamic_lds(K kernel, size_t dyn) {
-    // once per kernel instantiation and device (the caller's current one), the
-    // limit only grows.  Every wide instantiation has the same function type K,
-    // so the record is keyed by the kernel's address, not held per K.
-    static std::map<std::pair<const void*, int>, size_t> raised;
-    int d = 0;
-    (void)hipGetDevice(&d);
-    const void* const fn = reinterpret_cast<const void*>(kernel);
-    size_t& have = raised[{fn, d}];
-    if (dyn <= have) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    if (e == hipSuccess) have = dyn;
-    return e;
-}
-template <bool STATS>
-hipError_t extend_wide_prepare(int v, size_t dyn) {
-#define L_PREP(S) return raise_dynamic_lds(k_extend<S, STATS, true, BLOCK_WIDE>, dyn)
-    IGX_DISPATCH_VARIANT8(v, L_PREP);
-#undef L_PREP
-    return hipSuccess;
-}
-
-// The generate and bounce shapes of k_extend (host/extend_shape.h), one part
-// per LDS layout: the wide block (part 7), the BLOCK-thread kernel with
-// LDS-staged tables (part 8) and with global tables (part 9).  They share
-// launch bounds and static LDS with the generic instantiation of their
-// layout, so grids and the treelet are sized by the generic kernel's
-// resident blocks.
-void launch_extend_shaped_wide(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa,
-                               const PathBuf& in, const PathBuf& out, const KernelCounters& kc, int tail);
-hipError_t extend_shaped_wide_prepare(int v, size_t dyn);
-void launch_extend_shaped_lds(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa,
-                              const PathBuf& in, const PathBuf& out, const KernelCounters& kc, int tail);
-void launch_extend_shaped_global(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa,
-                                 const PathBuf& in, const PathBuf& out, const KernelCounters& kc, int tail);
-#define IGX_SHAPED(S, LDS_, BT_, dyn_, sv_)                                                                                        \
-    if (shape == EXTEND_GENERATE)                                                                                                  \
-        hipLaunchKernelGGL((k_extend<S, false, LDS_, BT_, EXTEND_GENERATE>), dim3(grid), dim3(BT_), dyn_, ctx.main, fa, sv_, in,    \
-                           out, s.sh, s.L, kc, tail);                                                                              \
-    else                                                                                                                           \
-        hipLaunchKernelGGL((k_extend<S, false, LDS_, BT_, EXTEND_BOUNCE>), dim3(grid), dim3(BT_), dyn_, ctx.main, fa, sv_, in,      \
-                           out, s.sh, s.L, kc, tail)
-#if IGX_PART == 7
-void launch_extend_shaped_wide(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa,
-                               const PathBuf& in, const PathBuf& out, const KernelCounters& kc, int tail) {
-    const size_t dyn = lds_pad16(dev->lds_scene_bytes) + dev->lds_shading_bytes;
-    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
-#define L_EXTW(S) IGX_SHAPED(S, true, BLOCK_WIDE, dyn, sv)
-    IGX_DISPATCH_VARIANT8(dev->variant, L_EXTW);
-#undef L_EXTW
-}
-hipError_t extend_shaped_wide_prepare(int v, size_t dyn) {
-#define L_PREP(S)                                                                                           \
-    {                                                                                                       \
-        const hipError_t e = raise_dynamic_lds(k_extend<S, false, true, BLOCK_WIDE, EXTEND_GENERATE>, dyn); \
-        return e != hipSuccess ? e : raise_dynamic_lds(k_extend<S, false, true, BLOCK_WIDE, EXTEND_BOUNCE>, dyn); \
+// The one switch from the scene's variant word to a kernel's template
+// argument: f is called with std::integral_constant<int, V> of the matching
+// case and its result returned.  Traversal kernels take the six traversal
+// variants (bit 7, VARIANT_Q4: quantised 4-wide nodes, only with bit 1) ...
+template <typename F>
+auto with_traversal_variant(int v, F&& f) {
+    switch (v & (3 | VARIANT_Q4)) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 2 | VARIANT_Q4: return f(std::integral_constant<int, 130>{});
+    default: return f(std::integral_constant<int, 131>{});
     }
-    IGX_DISPATCH_VARIANT8(v, L_PREP);
-#undef L_PREP
-    return hipSuccess;
+}
+// ... and shading kernels the twelve that add the material/light feature bit
+template <typename F>
+auto with_shading_variant(int v, F&& f) {
+    switch (v & (7 | VARIANT_Q4)) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 2 | VARIANT_Q4: return f(std::integral_constant<int, 130>{});
+    case 3 | VARIANT_Q4: return f(std::integral_constant<int, 131>{});
+    case 6 | VARIANT_Q4: return f(std::integral_constant<int, 134>{});
+    default: return f(std::integral_constant<int, 135>{});
+    }
+}
+
+// Which instantiation a launch runs is chosen once per kernel family, by a
+// chooser that returns what the launch, the occupancy query behind its grid
+// and the raise of its dynamic-LDS limit have to agree on.  All instantiations
+// of one kernel template share a signature, so the kernel travels as a typed
+// pointer.  A kernel's address is taken only in the part that holds its device
+// code: each part defines the choosers of its kernels (plain functions, declared
+// here for all parts), part 0 launches and queries what they return.
+using ExtendKernel = void (*)(FrameArgs, SceneView, PathBuf, PathBuf, ShadowBuf, float4*, KernelCounters, int);
+using TraceKernel = void (*)(FrameArgs, SceneView, PathBuf, HitBuf, const int*, int, unsigned long long*);
+using TraceRefillKernel = void (*)(FrameArgs, SceneView, PathBuf, HitBuf, const int*, int, unsigned long long*, int, int*);
+using ShadeKernel = void (*)(FrameArgs, SceneView, PathBuf, HitBuf, PathBuf, ShadowBuf, float4*, KernelCounters, int);
+using ShadowKernel = void (*)(SceneView, ShadowBuf, float4*, const int*, unsigned long long*, int*);
+using ShadowRefillKernel = void (*)(SceneView, ShadowBuf, float4*, const int*, unsigned long long*, int, int*);
+using FinishKernel = void (*)(FrameArgs, SceneView, PathBuf, float4*, const int*, int, unsigned long long*, unsigned long long*);
+using InfoKernel = void (*)(FrameArgs, SceneView, InfoArgs);
+template <typename K>
+const void* kernel_id(K kernel) { return reinterpret_cast<const void*>(kernel); }
+struct KernelChoice {
+    // the kernel whose resident blocks per CU size the grid: the launched one,
+    // except for the shaped k_extend and the if-if k_shadow_refill (below)
+    const void* sized_by = nullptr;
+    int block = BLOCK;
+    size_t dyn = 0; // dynamic LDS: the staged tables, or the treelet's tree_n nodes
+    int tree_n = 0; // SceneView::tree_n of the launch
+};
+struct ExtendChoice : KernelChoice { ExtendKernel kernel = nullptr; };
+// the split schedule's trace and the shadow kernel come with and without
+// persistent lanes, two templates with two signatures: one of the two is set
+struct TraceChoice : KernelChoice { TraceKernel kernel = nullptr; TraceRefillKernel refill = nullptr; };
+struct ShadowChoice : KernelChoice { ShadowKernel kernel = nullptr; ShadowRefillKernel refill = nullptr; };
+struct FinishChoice : KernelChoice { FinishKernel kernel = nullptr; };
+struct ShadeChoice : KernelChoice { ShadeKernel kernel = nullptr; };
+struct InfoChoice : KernelChoice { InfoKernel kernel = nullptr; };
+
+// k_extend spans five parts; each exports the pick among its instantiations
+// and choose_extend (part 0) combines them.  The generate and bounce shapes
+// (host/extend_shape.h) are never instrumented.
+ExtendKernel extend_kernel(int v, bool stats, bool lds);         // part 1: BLOCK threads, LDS-staged or global tables
+ExtendKernel extend_kernel_wide(int v, bool stats);              // part 4: BLOCK_WIDE threads, shading tables staged too
+ExtendKernel extend_kernel_shaped_wide(int v, ExtendShape shape);   // part 7
+ExtendKernel extend_kernel_shaped_lds(int v, ExtendShape shape);    // part 8
+ExtendKernel extend_kernel_shaped_global(int v, ExtendShape shape); // part 9
+ExtendChoice choose_extend(const igx_device* dev, bool stats, ExtendShape shape);
+TraceChoice choose_trace(const igx_device* dev, bool stats);   // part 3
+ShadowChoice choose_shadow(const igx_device* dev, bool stats); // part 3
+ShadeChoice choose_shade(bool full);                           // part 3
+FinishChoice choose_finish(const igx_device* dev, bool stats); // part 2
+InfoChoice choose_infobuffer(int v);                           // part 5
+
+#if IGX_PART == 1
+ExtendKernel extend_kernel(int v, bool stats, bool lds) {
+    return with_shading_variant(v, [&](auto V) -> ExtendKernel {
+        constexpr int S = decltype(V)::value;
+        if (lds) return stats ? k_extend<S, true, true> : k_extend<S, false, true>;
+        return stats ? k_extend<S, true, false> : k_extend<S, false, false>;
+    });
+}
+#endif
+#if IGX_PART == 4
+ExtendKernel extend_kernel_wide(int v, bool stats) {
+    return with_shading_variant(v, [&](auto V) -> ExtendKernel {
+        constexpr int S = decltype(V)::value;
+        return stats ? k_extend<S, true, true, BLOCK_WIDE> : k_extend<S, false, true, BLOCK_WIDE>;
+    });
+}
+#endif
+#if IGX_PART == 7
+ExtendKernel extend_kernel_shaped_wide(int v, ExtendShape shape) {
+    return with_shading_variant(v, [&](auto V) -> ExtendKernel {
+        constexpr int S = decltype(V)::value;
+        return shape == EXTEND_GENERATE ? k_extend<S, false, true, BLOCK_WIDE, EXTEND_GENERATE> : k_extend<S, false, true, BLOCK_WIDE, EXTEND_BOUNCE>;
+    });
 }
 #endif
 #if IGX_PART == 8
-void launch_extend_shaped_lds(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa,
-                              const PathBuf& in, const PathBuf& out, const KernelCounters& kc, int tail) {
-    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
-#define L_EXTL(S) IGX_SHAPED(S, true, BLOCK, dev->lds_scene_bytes, sv)
-    IGX_DISPATCH_VARIANT8(dev->variant, L_EXTL);
-#undef L_EXTL
+ExtendKernel extend_kernel_shaped_lds(int v, ExtendShape shape) {
+    return with_shading_variant(v, [&](auto V) -> ExtendKernel {
+        constexpr int S = decltype(V)::value;
+        return shape == EXTEND_GENERATE ? k_extend<S, false, true, BLOCK, EXTEND_GENERATE> : k_extend<S, false, true, BLOCK, EXTEND_BOUNCE>;
+    });
 }
 #endif
 #if IGX_PART == 9
-void launch_extend_shaped_global(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, ExtendShape shape, const FrameArgs& fa,
-                                 const PathBuf& in, const PathBuf& out, const KernelCounters& kc, int tail) {
-    SceneView tsv = launch_view(dev, ctx, ctx.spill_main);
-    tsv.tree_n = dev->tree_ext;
-#define L_EXT(S) IGX_SHAPED(S, false, BLOCK, tree_bytes(dev, tsv.tree_n), tsv)
-    IGX_DISPATCH_VARIANT8(dev->variant, L_EXT);
-#undef L_EXT
+ExtendKernel extend_kernel_shaped_global(int v, ExtendShape shape) {
+    return with_shading_variant(v, [&](auto V) -> ExtendKernel {
+        constexpr int S = decltype(V)::value;
+        return shape == EXTEND_GENERATE ? k_extend<S, false, false, BLOCK, EXTEND_GENERATE> : k_extend<S, false, false, BLOCK, EXTEND_BOUNCE>;
+    });
 }
 #endif
-#undef IGX_SHAPED
+
+#if IGX_PART == 2
+FinishChoice choose_finish(const igx_device* dev, bool stats) {
+    const bool lds = dev->lds_scene_bytes != 0, pairs = use_tail_pairs(dev); // pairs: global tables only
+    FinishChoice c;
+    c.dyn = dev->lds_scene_bytes; // the tail kernels stage no treelet (tree_n 0)
+    c.kernel = with_shading_variant(dev->variant, [&](auto V) -> FinishKernel {
+        constexpr int S = decltype(V)::value;
+        if (pairs) return stats ? k_finish_pairs<S, true> : k_finish_pairs<S, false>;
+        if (lds) return stats ? k_finish<S, true, true> : k_finish<S, false, true>;
+        return stats ? k_finish<S, true, false> : k_finish<S, false, false>;
+    });
+    c.sized_by = kernel_id(c.kernel);
+    return c;
+}
+#endif
+
+#if IGX_PART == 3
+TraceChoice choose_trace(const igx_device* dev, bool stats) {
+    const bool lds = dev->lds_scene_bytes != 0;
+    TraceChoice c;
+    c.dyn = dev->lds_scene_bytes; // on global tables neither kernel stages a treelet (tree_n 0)
+    with_traversal_variant(dev->variant, [&](auto V) {
+        constexpr int S = decltype(V)::value;
+        if (use_refill(dev)) {
+            if (lds) c.refill = stats ? k_trace_refill<S, true, true> : k_trace_refill<S, false, true>;
+            else c.refill = stats ? k_trace_refill<S, true, false> : k_trace_refill<S, false, false>;
+        } else {
+            // k_trace (the split schedule without persistent lanes): 5 waves per SIMD
+            // on global tables; LDS-staged tables set occupancy themselves
+            if (lds) c.kernel = stats ? k_trace<S, true, 1, true> : k_trace<S, false, 1, true>;
+            else c.kernel = stats ? k_trace<S, true, 5, false> : k_trace<S, false, 5, false>;
+        }
+    });
+    c.sized_by = c.refill ? kernel_id(c.refill) : kernel_id(c.kernel);
+    return c;
+}
+ShadowChoice choose_shadow(const igx_device* dev, bool stats) {
+    const bool lds = dev->lds_scene_bytes != 0;
+    ShadowChoice c;
+    c.tree_n = dev->tree_shadow;
+    c.dyn = lds ? dev->lds_scene_bytes : tree_bytes(dev, c.tree_n);
+    with_traversal_variant(dev->variant, [&](auto V) {
+        constexpr int S = decltype(V)::value;
+        if (use_refill(dev)) {
+            if (lds) c.refill = stats ? k_shadow_refill<S, true, true> : k_shadow_refill<S, false, true>;
+            else c.refill = stats ? k_shadow_refill<S, true, false> : k_shadow_refill<S, false, false>;
+            c.sized_by = kernel_id(c.refill);
+            // The if-if kernel (variant bit 4, SHADOW_IFIF_WAVES) keeps the grid of the
+            // while-while kernel (REFILL_WAVES) it replaces; no reason is recorded, and
+            // igx_stats::shadow_blocks_per_cu reports the same figure
+            if (!lds && use_shadow_ifif(dev)) c.refill = stats ? k_shadow_refill<S | 16, true, false> : k_shadow_refill<S | 16, false, false>;
+        } else {
+            if (lds) c.kernel = stats ? k_shadow<S, true, true> : k_shadow<S, false, true>;
+            else c.kernel = stats ? k_shadow<S, true, false> : k_shadow<S, false, false>;
+            c.sized_by = kernel_id(c.kernel);
+        }
+    });
+    return c;
+}
+ShadeChoice choose_shade(bool full) {
+    ShadeChoice c;
+    c.kernel = full ? k_shade<true> : k_shade<false>;
+    c.sized_by = kernel_id(c.kernel);
+    return c;
+}
+#endif
+
+#if IGX_PART == 5
+InfoChoice choose_infobuffer(int v) {
+    InfoChoice c;
+    c.kernel = with_shading_variant(v, [](auto V) -> InfoKernel { return k_infobuffer<decltype(V)::value>; });
+    c.sized_by = kernel_id(c.kernel); // its grids cover the film, no query
+    return c;
+}
+#endif
 
 // The shape of one k_extend launch: a pure function of the options and the
 // launch's FrameArgs (pick_extend_shape, host/extend_shape.h)
@@ -2835,209 +2910,6 @@ inline ExtendShape launch_shape(const igx_device* dev, bool instrumented, const 
     in.offsets_32bit = streams_offsets_32bit(out.shard_cap);
     return pick_extend_shape(in);
 }
-
-template <bool STATS>
-void launch_extend(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in,
-                   const PathBuf& out, const KernelCounters& kc, int tail) {
-    if (const ExtendShape shape = launch_shape(dev, STATS, fa, in, out, s.sh, kc); shape != EXTEND_GENERIC) {
-        ++dev->stats.launches_extend_shaped[shape == EXTEND_GENERATE ? 0 : 1];
-        if (dev->ext_block == BLOCK_WIDE) launch_extend_shaped_wide(dev, ctx, s, grid, shape, fa, in, out, kc, tail);
-        else if (dev->lds_scene_bytes) launch_extend_shaped_lds(dev, ctx, s, grid, shape, fa, in, out, kc, tail);
-        else launch_extend_shaped_global(dev, ctx, s, grid, shape, fa, in, out, kc, tail);
-        return;
-    }
-    if (dev->ext_block == BLOCK_WIDE) {
-        launch_extend_wide<STATS>(dev, ctx, s, grid, fa, in, out, kc, tail);
-        return;
-    }
-    SceneView tsv = launch_view(dev, ctx, ctx.spill_main);
-    if (dev->lds_scene_bytes) {
-#define L_EXTL(S) hipLaunchKernelGGL((k_extend<S, STATS, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, ctx.main, fa, tsv, in, out, s.sh, s.L, kc, tail)
-        IGX_DISPATCH_VARIANT8(dev->variant, L_EXTL);
-#undef L_EXTL
-        return;
-    }
-    tsv.tree_n = dev->tree_ext;
-#define L_EXT(S) hipLaunchKernelGGL((k_extend<S, STATS, false>), dim3(grid), dim3(BLOCK), tree_bytes(dev, tsv.tree_n), ctx.main, fa, tsv, in, out, s.sh, s.L, kc, tail)
-    IGX_DISPATCH_VARIANT8(dev->variant, L_EXT);
-#undef L_EXT
-}
-// k_trace (the split schedule without persistent lanes): 5 waves per SIMD on
-// global tables; LDS-staged tables set occupancy themselves
-template <bool STATS>
-void launch_trace(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in, const int* cnt,
-                  int tail, int* work) {
-    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
-    if (use_refill(dev)) {
-#define L_TRR(S)                                                                                                        \
-    if (dev->lds_scene_bytes)                                                                                            \
-        hipLaunchKernelGGL((k_trace_refill<S, STATS, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, ctx.main, fa,   \
-                           sv, in, s.hb, cnt, tail, dev->dstats, refill_min(dev), work);                                 \
-    else                                                                                                                 \
-        hipLaunchKernelGGL((k_trace_refill<S, STATS, false>), dim3(grid), dim3(BLOCK), 0, ctx.main, fa, sv, in, s.hb,        \
-                           cnt, tail, dev->dstats, refill_min(dev), work)
-        IGX_DISPATCH_VARIANT(dev->variant, L_TRR);
-#undef L_TRR
-        return;
-    }
-    if (dev->lds_scene_bytes) {
-#define L_TRL(S) hipLaunchKernelGGL((k_trace<S, STATS, 1, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, ctx.main, fa, sv, in, s.hb, cnt, tail, dev->dstats)
-        IGX_DISPATCH_VARIANT(dev->variant, L_TRL);
-#undef L_TRL
-        return;
-    }
-#define L_TR(S) hipLaunchKernelGGL((k_trace<S, STATS, 5, false>), dim3(grid), dim3(BLOCK), 0, ctx.main, fa, sv, in, s.hb, cnt, tail, dev->dstats)
-    IGX_DISPATCH_VARIANT(dev->variant, L_TR);
-#undef L_TR
-}
-template <bool STATS>
-void launch_shadow(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, const int* cnt, int* work) {
-    hipStream_t const strm = ctx.shadow;
-    SceneView tsv = launch_view(dev, ctx, ctx.spill_shadow); // its own columns where it overlaps the main stream's kernels
-    tsv.tree_n = dev->tree_shadow;
-    if (use_refill(dev)) {
-#define L_SHR(S)                                                                                                        \
-    if (dev->lds_scene_bytes)                                                                                            \
-        hipLaunchKernelGGL((k_shadow_refill<S, STATS, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, strm,   \
-                           tsv, s.sh, s.L, cnt, dev->dstats, refill_min(dev), work);                                 \
-    else                                                                                                                 \
-        hipLaunchKernelGGL((k_shadow_refill<S, STATS, false>), dim3(grid), dim3(BLOCK), tree_bytes(dev, tsv.tree_n), strm, \
-                           tsv, s.sh, s.L, cnt, dev->dstats, refill_min(dev), work)
-#define L_SHRI(S)                                                                                                       \
-    hipLaunchKernelGGL((k_shadow_refill<S | 16, STATS, false>), dim3(grid), dim3(BLOCK), tree_bytes(dev, tsv.tree_n), strm, \
-                       tsv, s.sh, s.L, cnt, dev->dstats, refill_min(dev), work)
-        if (!dev->lds_scene_bytes && use_shadow_ifif(dev)) IGX_DISPATCH_VARIANT(dev->variant, L_SHRI);
-        else IGX_DISPATCH_VARIANT(dev->variant, L_SHR);
-#undef L_SHRI
-#undef L_SHR
-        return;
-    }
-    if (dev->lds_scene_bytes) {
-#define L_SHL(S) hipLaunchKernelGGL((k_shadow<S, STATS, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, strm, tsv, s.sh, s.L, cnt, dev->dstats, work)
-        IGX_DISPATCH_VARIANT(dev->variant, L_SHL);
-#undef L_SHL
-        return;
-    }
-#define L_SH(S) hipLaunchKernelGGL((k_shadow<S, STATS, false>), dim3(grid), dim3(BLOCK), tree_bytes(dev, tsv.tree_n), strm, tsv, s.sh, s.L, cnt, dev->dstats, work)
-    IGX_DISPATCH_VARIANT(dev->variant, L_SH);
-#undef L_SH
-}
-template <bool STATS>
-void launch_finish(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, const FrameArgs& fa, const PathBuf& in, const int* cnt,
-                   int tail) {
-    SceneView tsv = launch_view(dev, ctx, ctx.spill_tail); // k_finish may run concurrently with the main stream's kernels
-    tsv.tree_n = 0;                                        // the tail kernels stage no treelet
-    if (dev->lds_scene_bytes) {
-#define L_FINL(S) hipLaunchKernelGGL((k_finish<S, STATS, true>), dim3(grid), dim3(BLOCK), dev->lds_scene_bytes, ctx.tail, fa, tsv, in, s.L, cnt, tail, dev->dstats, dev->tail_counts)
-        IGX_DISPATCH_VARIANT8(dev->variant, L_FINL);
-#undef L_FINL
-        return;
-    }
-    if (use_tail_pairs(dev)) {
-#define L_FINP(S) hipLaunchKernelGGL((k_finish_pairs<S, STATS>), dim3(grid), dim3(BLOCK), tree_bytes(dev, tsv.tree_n), ctx.tail, fa, tsv, in, s.L, cnt, tail, dev->dstats, dev->tail_counts)
-        IGX_DISPATCH_VARIANT8(dev->variant, L_FINP);
-#undef L_FINP
-        return;
-    }
-#define L_FIN(S) hipLaunchKernelGGL((k_finish<S, STATS, false>), dim3(grid), dim3(BLOCK), tree_bytes(dev, tsv.tree_n), ctx.tail, fa, tsv, in, s.L, cnt, tail, dev->dstats, dev->tail_counts)
-    IGX_DISPATCH_VARIANT8(dev->variant, L_FIN);
-#undef L_FIN
-}
-
-// resident blocks per CU of a kernel (persistent grid sizing)
-template <typename K>
-int resident_blocks(K kernel, size_t dyn_lds = 0, int block = BLOCK) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, dyn_lds) != hipSuccess || nb < 1) nb = 1;
-    return nb;
-}
-template <bool STATS>
-int extend_wide_blocks_per_cu(int v, size_t dyn) {
-#define L_RW(S) return resident_blocks(k_extend<S, STATS, true, BLOCK_WIDE>, dyn, BLOCK_WIDE)
-    IGX_DISPATCH_VARIANT8(v, L_RW);
-#undef L_RW
-    return 1;
-}
-#define IGX_RES1(K, V, ...) return lds ? resident_blocks(K<V, __VA_ARGS__, true>, lds) : resident_blocks(K<V, __VA_ARGS__, false>, tree)
-#define IGX_RESIDENT(K, ...)                                         \
-    do {                                                             \
-        switch (v & (3 | VARIANT_Q4)) {                              \
-        case 0: IGX_RES1(K, 0, __VA_ARGS__);                         \
-        case 1: IGX_RES1(K, 1, __VA_ARGS__);                         \
-        case 2: IGX_RES1(K, 2, __VA_ARGS__);                         \
-        case 3: IGX_RES1(K, 3, __VA_ARGS__);                         \
-        case 2 | VARIANT_Q4: IGX_RES1(K, 130, __VA_ARGS__);          \
-        default: IGX_RES1(K, 131, __VA_ARGS__);                      \
-        }                                                            \
-    } while (0)
-#define IGX_RESIDENT8(K, ...)                                        \
-    do {                                                             \
-        switch (v & (7 | VARIANT_Q4)) {                              \
-        case 0: IGX_RES1(K, 0, __VA_ARGS__);                         \
-        case 1: IGX_RES1(K, 1, __VA_ARGS__);                         \
-        case 2: IGX_RES1(K, 2, __VA_ARGS__);                         \
-        case 3: IGX_RES1(K, 3, __VA_ARGS__);                         \
-        case 4: IGX_RES1(K, 4, __VA_ARGS__);                         \
-        case 5: IGX_RES1(K, 5, __VA_ARGS__);                         \
-        case 6: IGX_RES1(K, 6, __VA_ARGS__);                         \
-        case 7: IGX_RES1(K, 7, __VA_ARGS__);                         \
-        case 2 | VARIANT_Q4: IGX_RES1(K, 130, __VA_ARGS__);          \
-        case 3 | VARIANT_Q4: IGX_RES1(K, 131, __VA_ARGS__);          \
-        case 6 | VARIANT_Q4: IGX_RES1(K, 134, __VA_ARGS__);          \
-        default: IGX_RES1(K, 135, __VA_ARGS__);                      \
-        }                                                            \
-    } while (0)
-#define IGX_RESIDENT_G(K) IGX_RESIDENT(K, STATS)
-template <bool STATS>
-int extend_blocks_per_cu(int v, size_t lds, size_t tree) { IGX_RESIDENT8(k_extend, STATS); }
-template <bool STATS>
-int shadow_blocks_per_cu(int v, size_t lds, bool refill, size_t tree) {
-    if (refill) IGX_RESIDENT_G(k_shadow_refill);
-    IGX_RESIDENT(k_shadow, STATS);
-}
-template <bool STATS>
-int finish_blocks_per_cu(int v, size_t lds, size_t tree, bool pairs) {
-    if (!lds && pairs) {
-#define L_RP(S) return resident_blocks(k_finish_pairs<S, STATS>, tree)
-        IGX_DISPATCH_VARIANT8(v, L_RP);
-#undef L_RP
-    }
-    IGX_RESIDENT8(k_finish, STATS);
-}
-template <bool STATS>
-int trace_blocks_per_cu(int v, size_t lds, bool refill) {
-    const size_t tree = 0; // no treelet (IGX_RES1)
-    if (refill) IGX_RESIDENT_G(k_trace_refill);
-    if (lds) IGX_RESIDENT(k_trace, STATS, 1);
-    IGX_RESIDENT(k_trace, STATS, 5);
-}
-#undef IGX_RESIDENT
-#undef IGX_RESIDENT8
-#undef IGX_RESIDENT_G
-
-void launch_shade(igx_device* dev, const LaunchCtx& ctx, bool full, int grid, const FrameArgs& fa, const PathBuf& in, const HitBuf& hb,
-                  const PathBuf& out, const ShadowBuf& sh, float4* L, const KernelCounters& kc, int tail);
-int shade_blocks_per_cu(bool full);
-#if IGX_PART == 3
-void launch_shade(igx_device* dev, const LaunchCtx& ctx, bool full, int grid, const FrameArgs& fa, const PathBuf& in, const HitBuf& hb,
-                  const PathBuf& out, const ShadowBuf& sh, float4* L, const KernelCounters& kc, int tail) {
-    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
-    if (full) hipLaunchKernelGGL(k_shade<true>, dim3(grid), dim3(BLOCK), 0, ctx.main, fa, sv, in, hb, out, sh, L, kc, tail);
-    else hipLaunchKernelGGL(k_shade<false>, dim3(grid), dim3(BLOCK), 0, ctx.main, fa, sv, in, hb, out, sh, L, kc, tail);
-}
-int shade_blocks_per_cu(bool full) { return full ? resident_blocks(k_shade<true>) : resident_blocks(k_shade<false>); }
-#endif
-
-// the info-buffer pass (k_infobuffer) on `strm`, for the scene view `sv` (the
-// caller's copy: its camera and the spill columns of that stream)
-void launch_infobuffer(igx_device* dev, int grid, hipStream_t strm, const FrameArgs& fa, const SceneView& sv, const InfoArgs& ia);
-#if IGX_PART == 5
-void launch_infobuffer(igx_device* dev, int grid, hipStream_t strm, const FrameArgs& fa, const SceneView& sv, const InfoArgs& ia) {
-#define L_IB(S) hipLaunchKernelGGL(k_infobuffer<S>, dim3(grid), dim3(BLOCK), 0, strm, fa, sv, ia)
-    IGX_DISPATCH_VARIANT8(dev->variant, L_IB);
-#undef L_IB
-}
-#endif
 
 // Film post-processing (igx_post.h, part 6): tone curve arguments, the
 // per-block partial results of the imageinfo passes (pass 1: one entry per
@@ -3089,54 +2961,6 @@ igx_glare_output glare_finish_slab(float* slab_host, size_t blocks, const igx_gl
 #include "igx_post.h"
 #endif
 
-// Launch helpers: defined (explicitly instantiated) in their part, extern elsewhere.
-#define IGX_EXTEND_HELPERS(X, S)                                                                                     \
-    X void launch_extend<S>(igx_device*, const LaunchCtx&, Slot&, int, const FrameArgs&, const PathBuf&, const PathBuf&, \
-                            const KernelCounters&, int);                                                             \
-    X int extend_blocks_per_cu<S>(int, size_t, size_t);
-#define IGX_FINISH_HELPERS(X, S)                                                                                     \
-    X void launch_finish<S>(igx_device*, const LaunchCtx&, Slot&, int, const FrameArgs&, const PathBuf&, const int*, int); \
-    X int finish_blocks_per_cu<S>(int, size_t, size_t, bool);
-#define IGX_TRACE_HELPERS(X, S)                                                                                      \
-    X void launch_trace<S>(igx_device*, const LaunchCtx&, Slot&, int, const FrameArgs&, const PathBuf&, const int*, int, int*); \
-    X void launch_shadow<S>(igx_device*, const LaunchCtx&, Slot&, int, const int*, int*);                             \
-    X int trace_blocks_per_cu<S>(int, size_t, bool);                                                                  \
-    X int shadow_blocks_per_cu<S>(int, size_t, bool, size_t);
-#define IGX_EXTEND_WIDE_HELPERS(X, S)                                                                                \
-    X void launch_extend_wide<S>(igx_device*, const LaunchCtx&, Slot&, int, const FrameArgs&, const PathBuf&, const PathBuf&, \
-                                 const KernelCounters&, int);                                                        \
-    X hipError_t extend_wide_prepare<S>(int, size_t);                                                                \
-    X int extend_wide_blocks_per_cu<S>(int, size_t);
-#if IGX_PART == 4
-IGX_EXTEND_WIDE_HELPERS(template, true)
-IGX_EXTEND_WIDE_HELPERS(template, false)
-#else
-IGX_EXTEND_WIDE_HELPERS(extern template, true)
-IGX_EXTEND_WIDE_HELPERS(extern template, false)
-#endif
-#if IGX_PART == 1
-IGX_EXTEND_HELPERS(template, true)
-IGX_EXTEND_HELPERS(template, false)
-#else
-IGX_EXTEND_HELPERS(extern template, true)
-IGX_EXTEND_HELPERS(extern template, false)
-#endif
-#if IGX_PART == 2
-IGX_FINISH_HELPERS(template, true)
-IGX_FINISH_HELPERS(template, false)
-#else
-IGX_FINISH_HELPERS(extern template, true)
-IGX_FINISH_HELPERS(extern template, false)
-#endif
-#if IGX_PART == 3
-IGX_TRACE_HELPERS(template, true)
-IGX_TRACE_HELPERS(template, false)
-#else
-IGX_TRACE_HELPERS(extern template, true)
-IGX_TRACE_HELPERS(extern template, false)
-#endif
-#undef IGX_RES1
-
 // k_camera_rays (part 10) on dev->stream: `rays` takes 2 float4 per pixel of fa's film
 void launch_camera_rays(igx_device* dev, int grid, const FrameArgs& fa, const SceneView& sv, float4* rays);
 #if IGX_PART == 10
@@ -3146,6 +2970,100 @@ void launch_camera_rays(igx_device* dev, int grid, const FrameArgs& fa, const Sc
 #endif
 
 #if IGX_PART == 0
+// k_extend for the current LDS layout (configure_lds) and the launch's shape.
+// The generate and bounce shapes share launch bounds and static LDS with the
+// generic instantiation of their layout, so grids and the treelet are sized by
+// the generic kernel's resident blocks.
+ExtendChoice choose_extend(const igx_device* dev, bool stats, ExtendShape shape) {
+    const int v = dev->variant;
+    const bool shaped = shape != EXTEND_GENERIC, lds = dev->lds_scene_bytes != 0;
+    ExtendChoice c;
+    ExtendKernel generic;
+    if (dev->ext_block == BLOCK_WIDE) {
+        generic = extend_kernel_wide(v, stats);
+        c.kernel = shaped ? extend_kernel_shaped_wide(v, shape) : generic;
+        c.block = BLOCK_WIDE;
+        c.dyn = lds_pad16(dev->lds_scene_bytes) + dev->lds_shading_bytes;
+    } else if (lds) {
+        generic = extend_kernel(v, stats, true);
+        c.kernel = shaped ? extend_kernel_shaped_lds(v, shape) : generic;
+        c.dyn = dev->lds_scene_bytes;
+    } else {
+        generic = extend_kernel(v, stats, false);
+        c.kernel = shaped ? extend_kernel_shaped_global(v, shape) : generic;
+        c.tree_n = dev->tree_ext;
+        c.dyn = tree_bytes(dev, c.tree_n);
+    }
+    c.sized_by = kernel_id(generic);
+    return c;
+}
+
+// resident blocks per CU of a kernel (persistent grid sizing)
+int resident_blocks(const void* kernel, size_t dyn_lds, int block) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, dyn_lds) != hipSuccess || nb < 1) nb = 1;
+    return nb;
+}
+int blocks_per_cu(const KernelChoice& c) { return resident_blocks(c.sized_by, c.dyn, c.block); }
+// a block above 64 KB needs its kernel's dynamic-LDS limit raised
+hipError_t raise_dynamic_lds(const void* kernel, size_t dyn) {
+    // once per kernel instantiation and device (the caller's current one), the
+    // limit only grows
+    static std::map<std::pair<const void*, int>, size_t> raised;
+    int d = 0;
+    (void)hipGetDevice(&d);
+    size_t& have = raised[{kernel, d}];
+    if (dyn <= have) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+    if (e == hipSuccess) have = dyn;
+    return e;
+}
+
+void launch_extend(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, bool stats, const FrameArgs& fa, const PathBuf& in,
+                   const PathBuf& out, const KernelCounters& kc, int tail) {
+    const ExtendShape shape = launch_shape(dev, stats, fa, in, out, s.sh, kc);
+    if (shape != EXTEND_GENERIC) ++dev->stats.launches_extend_shaped[shape == EXTEND_GENERATE ? 0 : 1];
+    const ExtendChoice c = choose_extend(dev, stats, shape);
+    SceneView sv = launch_view(dev, ctx, ctx.spill_main);
+    sv.tree_n = c.tree_n;
+    hipLaunchKernelGGL(c.kernel, dim3(grid), dim3(c.block), c.dyn, ctx.main, fa, sv, in, out, s.sh, s.L, kc, tail);
+}
+void launch_trace(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, bool stats, const FrameArgs& fa, const PathBuf& in,
+                  const int* cnt, int tail, int* work) {
+    const TraceChoice c = choose_trace(dev, stats);
+    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
+    if (c.refill)
+        hipLaunchKernelGGL(c.refill, dim3(grid), dim3(c.block), c.dyn, ctx.main, fa, sv, in, s.hb, cnt, tail, dev->dstats, refill_min(dev), work);
+    else hipLaunchKernelGGL(c.kernel, dim3(grid), dim3(c.block), c.dyn, ctx.main, fa, sv, in, s.hb, cnt, tail, dev->dstats);
+}
+void launch_shade(igx_device* dev, const LaunchCtx& ctx, bool full, int grid, const FrameArgs& fa, const PathBuf& in, const HitBuf& hb,
+                  const PathBuf& out, const ShadowBuf& sh, float4* L, const KernelCounters& kc, int tail) {
+    const ShadeChoice c = choose_shade(full);
+    const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
+    hipLaunchKernelGGL(c.kernel, dim3(grid), dim3(c.block), c.dyn, ctx.main, fa, sv, in, hb, out, sh, L, kc, tail);
+}
+void launch_shadow(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, bool stats, const int* cnt, int* work) {
+    const ShadowChoice c = choose_shadow(dev, stats);
+    SceneView sv = launch_view(dev, ctx, ctx.spill_shadow); // its own columns where it overlaps the main stream's kernels
+    sv.tree_n = c.tree_n;
+    if (c.refill)
+        hipLaunchKernelGGL(c.refill, dim3(grid), dim3(c.block), c.dyn, ctx.shadow, sv, s.sh, s.L, cnt, dev->dstats, refill_min(dev), work);
+    else hipLaunchKernelGGL(c.kernel, dim3(grid), dim3(c.block), c.dyn, ctx.shadow, sv, s.sh, s.L, cnt, dev->dstats, work);
+}
+void launch_finish(igx_device* dev, const LaunchCtx& ctx, Slot& s, int grid, bool stats, const FrameArgs& fa, const PathBuf& in,
+                   const int* cnt, int tail) {
+    const FinishChoice c = choose_finish(dev, stats);
+    SceneView sv = launch_view(dev, ctx, ctx.spill_tail); // k_finish may run concurrently with the main stream's kernels
+    sv.tree_n = c.tree_n;
+    hipLaunchKernelGGL(c.kernel, dim3(grid), dim3(c.block), c.dyn, ctx.tail, fa, sv, in, s.L, cnt, tail, dev->dstats, dev->tail_counts);
+}
+// the info-buffer pass (k_infobuffer) on `strm`, for the scene view `sv` (the
+// caller's copy: its camera and the spill columns of that stream)
+void launch_infobuffer(igx_device* dev, int grid, hipStream_t strm, const FrameArgs& fa, const SceneView& sv, const InfoArgs& ia) {
+    const InfoChoice c = choose_infobuffer(dev->variant);
+    hipLaunchKernelGGL(c.kernel, dim3(grid), dim3(c.block), c.dyn, strm, fa, sv, ia);
+}
+
 // k_generate on the main stream, with the camera models of the scene's shading variant
 void launch_generate(igx_device* dev, const LaunchCtx& ctx, int grid, const FrameArgs& fa, const PathBuf& out, float4* L, int* cnt0) {
     const SceneView sv = launch_view(dev, ctx, ctx.spill_main);
@@ -3236,27 +3154,33 @@ void configure_lds(igx_device* dev) {
     in.stack_bytes_per_thread = LDS_STACK * sizeof(int);
     in.fixed_bytes = EXTEND_FIXED_LDS;
     in.lds_per_block = dev->lds_per_block;
-    LdsPlan p = plan_lds(in);
-    if (p.block_threads == BLOCK_WIDE) {
-        // a block above 64 KB: raise the instantiations' dynamic-LDS limit once;
-        // a refusal keeps today's layout; the text in last_error is advisory
-        // (the call that got here still returns IGX_OK)
-        const size_t dyn = lds_pad16(p.traversal_bytes) + p.shading_bytes;
+    const LdsPlan p = plan_lds(in);
+    dev->lds_scene_bytes = p.traversal_bytes;
+    dev->lds_shading_bytes = p.shading_bytes;
+    dev->ext_block = p.block_threads;
+    if (dev->ext_block == BLOCK_WIDE) {
+        // a block above 64 KB: raise the dynamic-LDS limit of the wide kernels
+        // this layout can launch (generic plain and instrumented, generate,
+        // bounce), stopping at the first refusal; a refusal keeps today's
+        // layout; the text in last_error is advisory (the call that got here
+        // still returns IGX_OK)
         (void)hipSetDevice(dev->hip_device);
-        hipError_t e = extend_wide_prepare<false>(dev->variant, dyn);
-        if (e == hipSuccess) e = extend_wide_prepare<true>(dev->variant, dyn);
-        if (e == hipSuccess) e = extend_shaped_wide_prepare(dev->variant, dyn);
+        const std::pair<bool, ExtendShape> wide[] = {
+            {false, EXTEND_GENERIC}, {true, EXTEND_GENERIC}, {false, EXTEND_GENERATE}, {false, EXTEND_BOUNCE}};
+        hipError_t e = hipSuccess;
+        for (const auto& [stats, shape] : wide) {
+            if (e != hipSuccess) break;
+            const ExtendChoice c = choose_extend(dev, stats, shape);
+            e = raise_dynamic_lds(kernel_id(c.kernel), c.dyn);
+        }
         if (e != hipSuccess) {
             (void)hipGetLastError();
             dev->last_error = std::string("lds_shading: the wide k_extend's LDS block was refused (") + hipGetErrorString(e) +
                               "); keeping the 256-thread layout";
-            p.block_threads = BLOCK;
-            p.shading_bytes = 0;
+            dev->ext_block = BLOCK;
+            dev->lds_shading_bytes = 0;
         }
     }
-    dev->lds_scene_bytes = p.traversal_bytes;
-    dev->lds_shading_bytes = p.shading_bytes;
-    dev->ext_block = p.block_threads;
 }
 
 // Treelet size of every global-table kernel: the largest prefix of the hot
@@ -3269,22 +3193,21 @@ void configure_treelet(igx_device* dev) {
     if (!dev->has_scene || dev->lds_scene_bytes || dev->treelet_opt == 0) return;
     int cap = (int)std::min<size_t>(TREELET_FRONT, (size_t)dev->sv.num_nodes);
     if (dev->treelet_opt > 0) cap = (int)std::min<int64_t>(cap, dev->treelet_opt);
-    const int v = dev->variant;
-    const bool refill = use_refill(dev);
-    auto fit = [&](auto blocks) {
-        const int nb0 = blocks((size_t)0);
+    // asked of the uninstrumented choice's grid-sizing kernel
+    auto fit = [&](const KernelChoice& c) {
+        const int nb0 = resident_blocks(c.sized_by, 0, c.block);
         int lo = 0, hi = cap;
         while (lo < hi) {
             const int mid = (lo + hi + 1) / 2;
-            if (blocks(tree_bytes(dev, mid)) >= nb0) lo = mid;
+            if (resident_blocks(c.sized_by, tree_bytes(dev, mid), c.block) >= nb0) lo = mid;
             else hi = mid - 1;
         }
         return lo;
     };
-    if (EXTEND_TREELET) dev->tree_ext = fit([&](size_t t) { return extend_blocks_per_cu<false>(v, 0, t); });
+    if (EXTEND_TREELET) dev->tree_ext = fit(choose_extend(dev, false, EXTEND_GENERIC));
     // the if-if shadow kernel of the split schedule: global node loads beat a
     // treelet's flat loads there (profiles/r03_ab_treelet_global.log)
-    if (SHADOW_TREELET && !(refill && use_shadow_ifif(dev))) dev->tree_shadow = fit([&](size_t t) { return shadow_blocks_per_cu<false>(v, 0, refill, t); });
+    if (SHADOW_TREELET && !(use_refill(dev) && use_shadow_ifif(dev))) dev->tree_shadow = fit(choose_shadow(dev, false));
     // k_trace_refill and the tail kernels: none -- the tail kernel overlaps the
     // next chunk's kernels, and LDS it holds keeps their blocks off the CU
     // (soup-1M frame +4 % with one)
@@ -3856,8 +3779,7 @@ static igx_status queue_bounce(igx_device* dev, const LaunchCtx& ctx, Slot& S, c
         const int tr_grid = grid_for(dev, bound, pl.tr_bpc), shade_grid = grid_for(dev, bound, pl.shade_bpc);
         begin_timed(dev, S, 5, b, ctx.main);
         int* const tr_work = (dev->dynamic_opt & DYN_REFILL_TRACE) ? ctr_row(S, WORK_ROW0 + 4 * b) : nullptr;
-        if (inst) launch_trace<true>(dev, ctx, S, tr_grid, r.fa, in, ctr_row(S, 2 * b), r.tail, tr_work);
-        else launch_trace<false>(dev, ctx, S, tr_grid, r.fa, in, ctr_row(S, 2 * b), r.tail, tr_work);
+        launch_trace(dev, ctx, S, tr_grid, inst, r.fa, in, ctr_row(S, 2 * b), r.tail, tr_work);
         end_timed(dev, S, ctx.main);
         if (r.sh_done) HIPCHK(hipStreamWaitEvent(ctx.main, r.sh_done, 0));
         begin_timed(dev, S, 0, b, ctx.main);
@@ -3868,8 +3790,7 @@ static igx_status queue_bounce(igx_device* dev, const LaunchCtx& ctx, Slot& S, c
         begin_timed(dev, S, 0, b, ctx.main);
         FrameArgs fb = r.fa;
         fb.gen_n = r.fuse_gen && b == 0 ? (int)r.n : 0;
-        if (inst) launch_extend<true>(dev, ctx, S, ext_grid, fb, in, out, kc, r.tail);
-        else launch_extend<false>(dev, ctx, S, ext_grid, fb, in, out, kc, r.tail);
+        launch_extend(dev, ctx, S, ext_grid, inst, fb, in, out, kc, r.tail);
         end_timed(dev, S, ctx.main);
     }
     if (overlap) {
@@ -3880,8 +3801,7 @@ static igx_status queue_bounce(igx_device* dev, const LaunchCtx& ctx, Slot& S, c
     begin_timed(dev, S, 1, b, ctx.shadow);
     int* const sh_work =
         (dev->dynamic_opt & (use_refill(dev) ? DYN_REFILL_SHADOW : DYN_SHADOW)) ? ctr_row(S, WORK_ROW0 + 4 * b + 2) : nullptr;
-    if (inst) launch_shadow<true>(dev, ctx, S, sh_grid, ctr_row(S, 2 * b + 1), sh_work);
-    else launch_shadow<false>(dev, ctx, S, sh_grid, ctr_row(S, 2 * b + 1), sh_work);
+    launch_shadow(dev, ctx, S, sh_grid, inst, ctr_row(S, 2 * b + 1), sh_work);
     end_timed(dev, S, ctx.shadow);
     if (overlap) {
         r.sh_done = slot_event(S);
@@ -3912,8 +3832,7 @@ static igx_status queue_tail(igx_device* dev, const LaunchCtx& ctx, Slot& S, con
     if (switch_b >= MAX_BOUNCES) return IGX_OK;
     PathBuf in = (switch_b & 1) ? S.pb : S.pa;
     begin_timed(dev, S, 4, switch_b, ctx.tail);
-    if (dev->instrument) launch_finish<true>(dev, ctx, S, r.fin_grid, r.fa, in, ctr_row(S, 2 * switch_b), r.tail);
-    else launch_finish<false>(dev, ctx, S, r.fin_grid, r.fa, in, ctr_row(S, 2 * switch_b), r.tail);
+    launch_finish(dev, ctx, S, r.fin_grid, dev->instrument, r.fa, in, ctr_row(S, 2 * switch_b), r.tail);
     end_timed(dev, S, ctx.tail);
     HIPCHK(hipGetLastError());
     return IGX_OK;
@@ -4344,22 +4263,14 @@ static igx_status render_impl(igx_device* dev, const igx_render_params* p, int c
     plan.aov = want_aov;
     plan.max_bounces = std::min(std::max(dev->sv.max_depth, 1), MAX_BOUNCES - 1);
     const bool inst = dev->instrument;
-    const int sd = dev->variant;
-    const size_t ldsb = dev->lds_scene_bytes;
     if (dev->tree_dirty) configure_treelet(dev);
-    const size_t wide_dyn = lds_pad16(ldsb) + dev->lds_shading_bytes;
-    plan.ext_bpc = dev->ext_block == BLOCK_WIDE
-                       ? (inst ? extend_wide_blocks_per_cu<true>(sd, wide_dyn) : extend_wide_blocks_per_cu<false>(sd, wide_dyn))
-                       : (inst ? extend_blocks_per_cu<true>(sd, ldsb, tree_bytes(dev, dev->tree_ext))
-                               : extend_blocks_per_cu<false>(sd, ldsb, tree_bytes(dev, dev->tree_ext)));
-    const bool refill = use_refill(dev);
-    plan.tr_bpc = inst ? trace_blocks_per_cu<true>(sd, ldsb, refill) : trace_blocks_per_cu<false>(sd, ldsb, refill);
-    plan.full = variant_full(sd);
-    plan.shade_bpc = shade_blocks_per_cu(plan.full);
-    plan.sh_bpc = inst ? shadow_blocks_per_cu<true>(sd, ldsb, refill, tree_bytes(dev, dev->tree_shadow))
-                       : shadow_blocks_per_cu<false>(sd, ldsb, refill, tree_bytes(dev, dev->tree_shadow));
+    plan.ext_bpc = blocks_per_cu(choose_extend(dev, inst, EXTEND_GENERIC));
+    plan.tr_bpc = blocks_per_cu(choose_trace(dev, inst));
+    plan.full = variant_full(dev->variant);
+    plan.shade_bpc = blocks_per_cu(choose_shade(plan.full));
+    plan.sh_bpc = blocks_per_cu(choose_shadow(dev, inst));
     plan.pairs = use_tail_pairs(dev);
-    plan.fin_bpc = inst ? finish_blocks_per_cu<true>(sd, ldsb, 0, plan.pairs) : finish_blocks_per_cu<false>(sd, ldsb, 0, plan.pairs);
+    plan.fin_bpc = blocks_per_cu(choose_finish(dev, inst));
 
     if (conc) {
         dev->iteration_count += count;
@@ -4873,8 +4784,7 @@ extern "C" igx_status igx_get_stats(igx_device* dev, igx_stats* out) {
     out->lds_shading_bytes = (int32_t)dev->lds_shading_bytes;
     out->extend_block_threads = dev->ext_block;
     if (dev->has_scene && dev->tree_dirty) configure_treelet(dev);
-    out->shadow_blocks_per_cu = dev->has_scene ? shadow_blocks_per_cu<false>(dev->variant, dev->lds_scene_bytes, use_refill(dev),
-                                                                            tree_bytes(dev, dev->tree_shadow)) : 0;
+    out->shadow_blocks_per_cu = dev->has_scene ? blocks_per_cu(choose_shadow(dev, false)) : 0;
     out->treelet_nodes[0] = dev->tree_ext;
     out->treelet_nodes[1] = 0; // k_trace_refill: no treelet
     out->treelet_nodes[2] = dev->tree_shadow;
@@ -4932,9 +4842,9 @@ static igx_status trace_batch(igx_device* dev, const float* rays, int32_t n, uin
         HIPCHK(hipEventCreate(&e1));
         HIPCHK(hipEventRecord(e0, dev->stream));
     }
-#define L_TH(S) hipLaunchKernelGGL(k_trace_hits<S>, dim3(grid), dim3(BLOCK), 0, dev->stream, dev->sv, d_rays, n, flags, d_ep, d_tuv, any)
-    IGX_DISPATCH_VARIANT(dev->variant, L_TH);
-#undef L_TH
+    with_traversal_variant(dev->variant, [&](auto V) {
+        hipLaunchKernelGGL(k_trace_hits<decltype(V)::value>, dim3(grid), dim3(BLOCK), 0, dev->stream, dev->sv, d_rays, n, flags, d_ep, d_tuv, any);
+    });
     HIPCHK(hipGetLastError());
     if (e1) HIPCHK(hipEventRecord(e1, dev->stream));
     HIPCHK(hipStreamSynchronize(dev->stream));
